@@ -9,6 +9,12 @@ N GPUs = N independent replicas, episodes sharded by rank (weak scaling, no data
 collective).
 
     python bench.py [--gpus N --steps K --warmup W] [--shot 5] [--layers 101 --size 641]
+
+A plain run sets up, warms up, times the K steps and prints the headline result line.
+--dump-outputs DIR also writes the last timed step's results as DIR/<name>.npy (the inputs are
+seeded, so two builds can be compared output for output).  --full adds every side study to the
+line: the sequential leg, the batched pipeline, the exact-fp32 and bf16x3 legs, the per-launch
+and roofline records, the inner loop's latency floor and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -34,6 +40,35 @@ ARITH_X3S, ARITH_F32, ARITH_X6 = 0, 1, 2                # CWT_CONV_ARITH_* (incl
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # array bytes; with the .npy headers the files stay under 64 MB (10^6)
+DUMP_SAMPLE_SEED = 2021
+
+
+def dump_outputs(dirname: str, result: dict) -> dict:
+    """--dump-outputs: write every tensor of the last timed step's result (what the timed path
+    handed its caller) as dirname/<name>.npy, float32 (float64 for float64 and integer tensors),
+    DUMP_BUDGET_BYTES in all.  An array larger than its share of the budget is stored as a fixed
+    sample: the elements at the sorted flat indices default_rng(DUMP_SAMPLE_SEED).integers(0,
+    size, share), the same in every run of the same arguments.  Returns {name: stored shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, t in result.items():
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        arrs[name] = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    share = DUMP_BUDGET_BYTES // max(len(arrs), 1)
+    shapes = {}
+    for name, a in arrs.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def host_cpu_info() -> dict:
@@ -394,7 +429,9 @@ def main_pretrain(args, dev, rank, world, cdist):
                      "flops_per_step": flops_step, "event_ms_per_step": round(ev_ms, 3)},
         "loss_last": round(float(losses[-1]), 5),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"loss": losses[-1]})
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_pretrain(layers, S, nc)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -515,8 +552,18 @@ def main():
     ap.add_argument("--pair-steps", type=int, default=20,
                     help="steps of the batched-pipeline leg (two episodes share one extractor pass, "
                          "EpisodePipeline.submit_batch; reported beside the headline); 0 = skip")
-    ap.add_argument("--profile-json", default=None, help="write per-launch records here (rank 0)")
+    ap.add_argument("--profile-json", default=None, help="write per-launch records here (rank 0; needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side study (the sequential leg, the batched "
+                         "pipeline, the exact-fp32 and bf16x3 legs, per-launch and roofline records, the latency "
+                         "floor, the CPU baseline) and report them in the result line; a plain run sets up, warms "
+                         "up, times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64, rank 0)")
     args = ap.parse_args()
+    if args.profile_json and not args.full:
+        ap.error("--profile-json holds the per-launch records of --full's extra episodes: add --full")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -585,6 +632,7 @@ def main():
     bound = 1.0 / np.sqrt(512)
     W0 = ((torch.rand((nW, E, 2, 512), generator=g) * 2 - 1) * bound).to(dev)
     torch.cuda.synchronize()
+    newest = {}   # "result": what the newest step handed its caller (--dump-outputs reads the last timed one)
 
     def step(i: int, Wbuf, last: bool = False):
         imgs, sl, ql = pool[i % len(pool)]
@@ -595,12 +643,16 @@ def main():
             else:
                 r = tengine.step(imgs, sl[0], ql, Wbuf[0])
                 after()
+            newest["result"] = r
             return r["loss"].view(1, 1, 1).expand(1, 2, 2)
         if pipe is not None:
-            return pipe.submit(imgs, sl[0], ql, Wbuf[0], last=last)["iut"]
-        if E == 1:
-            return engine.run(imgs, sl[0], ql, Wbuf[0])["iut"]
-        return engine.run_batch(imgs, sl, ql, Wbuf)["iut"]
+            r = pipe.submit(imgs, sl[0], ql, Wbuf[0], last=last)
+        elif E == 1:
+            r = engine.run(imgs, sl[0], ql, Wbuf[0])
+        else:
+            r = engine.run_batch(imgs, sl, ql, Wbuf)
+        newest["result"] = r
+        return r["iut"]
 
     # warm-up runs exactly the timed loop's code (lazy kernel loading, graph capture, workspaces)
     warm_iut = [step(s, W0[s], last=s == args.warmup - 1) for s in range(args.warmup)]
@@ -625,6 +677,56 @@ def main():
     value = world * args.steps * E / dt
     seq = None
     recs = _lib.profile_records()
+    _lib.profile_enable(0)
+    dom = [r for r in recs if r[0].startswith("conv_igemm")]     # the bottleneck conv (level 1 records only it)
+    dom_name = dom[0][0].split(" ")[0] if dom else "n/a"
+    conv_x3 = dom_name.startswith("conv_igemm_bf16x3") or dom_name.startswith("conv_igemm_x3s")
+    conv_x6 = dom_name.startswith("conv_igemm_x6")
+    conv_b16 = dom_name.startswith("conv_igemm_b16")
+    iu = torch.cat(iuts).sum(0)
+    head = {
+        "metric": (f"training episodes/sec ({S}x{S}, {shot}-shot, R{layers})" if args.train else
+                   "episodes/sec (473x473, 1-shot, R50) at 1/2/4/8 MI355X; mIoU vs ref"
+                   if (S, shot, layers) == (473, 1, 50) else f"episodes/sec ({S}x{S}, {shot}-shot, R{layers})")
+        + (" [bf16 conv stack]" if args.conv_dtype == "bf16" else ""),
+        "value": round(value, 3),
+        "unit": "training episodes/s" if args.train else "episodes/s",
+        "n_gpus": cdist.rank_world()[1],
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("fp32 (conv stack at fp32 width on the bf16 MFMA: every fp32 operand split exactly into bf16 "
+                  "hi + mid + lo, the six products >= 2^-24 |a||b| summed in fp32; inner loop, CWT, classifier "
+                  "fp32)") if conv_x6
+        else "fp32 (conv stack: bf16x3 split-fp32 on bf16 MFMA, ~16-bit operands)" if conv_x3
+        else "bf16 conv stack (fp32 accumulate) + fp32 inner loop / CWT / classifier" if conv_b16 else "fp32",
+        "data": "synthetic (PRNG weights + PASCAL-shaped episodes, few_shot_seg_cwt_amd/synthetic.py)",
+        "config": {"workload": (f"CWT training episode (do_epoch, batch_size=1, RCCL mean all-reduce of the "
+                                f"8.39 MB gradient bucket + nesterov SGD per step): " if args.train else
+                                f"CWT inference episode (validate_transformer, batch_size_val=1): ") +
+                               f"{'PASCAL split-0' if layers == 50 else 'COCO-20i split-0'} {shot}-shot "
+                               f"ResNet-{layers} PSPNet {S}x{S}, adapt_iter 200, heads 4",
+                   "image_size": S, "shot": shot, "layers": layers, "episodes_per_step_per_gpu": E,
+                   "parallelism": f"{world} episode-sharded replicas" + (f", {E} episodes in flight per GPU" if E > 1 else "")
+                   + (f", episode pipeline ({args.pipeline} extractor stream(s) beside the inner-loop / CWT stream: "
+                      "episode i+1's extractor pass overlaps episode i's inner loop, each episode alone)"
+                      if pipe is not None else "")},
+        "iou_fg_timed": None if args.train else round(float((iu[0, 1] / iu[1, 1].clamp_min(1)).item()), 4),
+        "host_submit_ms_per_step": round((t_sub - t0) / args.steps * 1e3, 3),
+        "full": args.full,
+    }
+    if rank == 0 and args.dump_outputs:   # before any other leg reuses the workspaces behind these tensors
+        head["dumped_outputs"] = dump_outputs(args.dump_outputs, newest["result"])
+    if not args.full:   # a plain run: the headline alone (the side studies and the CPU baseline: --full)
+        _lib.check_status()   # every launch has completed: surface an inner-loop barrier timeout
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     seq_recs = None
     if pipe is not None:   # the same episodes one after the other on one stream (no overlap), same run
         pipe_saved, pipe = pipe, None
@@ -690,7 +792,6 @@ def main():
                                 **conv_roofline(pfine, PEAK_BF16_MFMA_TFLOPS if args.conv_dtype == "bf16"
                                                 else PEAK_X6_TFLOPS)}}
         del pouts
-    iu = torch.cat(iuts).sum(0)
 
     def total(prefix):
         sel = [r for r in recs if r[0].startswith(prefix)]
@@ -703,12 +804,7 @@ def main():
     n_tl, _, tl_ms = total("post_loop_tail")  # the one-launch tail (CWT + classifier + metrics)
     n_tk, _, tk_ms = total("episode_tail_kernel")
     tk_sel = [r for r in recs if r[0].startswith("episode_tail_kernel")]
-    dom = [r for r in recs if r[0].startswith("conv_igemm")]     # the bottleneck conv (level 1 records only it)
-    dom_name = dom[0][0].split(" ")[0] if dom else "n/a"
     dn, dfl, dms = len(dom), sum(r[1] for r in dom), sum(r[3] for r in dom)
-    conv_x3 = dom_name.startswith("conv_igemm_bf16x3") or dom_name.startswith("conv_igemm_x3s")
-    conv_x6 = dom_name.startswith("conv_igemm_x6")
-    conv_b16 = dom_name.startswith("conv_igemm_b16")
     achieved = (dfl / dn) / (dms / dn * 1e-3) / 1e12
     if conv_x6:   # fp32 width as 6 bf16 MFMA products: the roof is the dense bf16 rate / 6
         peak, peak_basis = PEAK_X6_TFLOPS, "bf16x6: 2516.6 TF dense bf16 MFMA / 6 products"
@@ -958,35 +1054,7 @@ def main():
         bf16x3["arithmetic"] = "bf16x3 (approximation)"
 
     out = {
-        "metric": (f"training episodes/sec ({S}x{S}, {shot}-shot, R{layers})" if args.train else
-                   "episodes/sec (473x473, 1-shot, R50) at 1/2/4/8 MI355X; mIoU vs ref"
-                   if (S, shot, layers) == (473, 1, 50) else f"episodes/sec ({S}x{S}, {shot}-shot, R{layers})")
-        + (" [bf16 conv stack]" if args.conv_dtype == "bf16" else ""),
-        "value": round(value, 3),
-        "unit": "training episodes/s" if args.train else "episodes/s",
-        "n_gpus": cdist.rank_world()[1],
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("fp32 (conv stack at fp32 width on the bf16 MFMA: every fp32 operand split exactly into bf16 "
-                  "hi + mid + lo, the six products >= 2^-24 |a||b| summed in fp32; inner loop, CWT, classifier "
-                  "fp32)") if conv_x6
-        else "fp32 (conv stack: bf16x3 split-fp32 on bf16 MFMA, ~16-bit operands)" if conv_x3
-        else "bf16 conv stack (fp32 accumulate) + fp32 inner loop / CWT / classifier" if conv_b16 else "fp32",
-        "data": "synthetic (PRNG weights + PASCAL-shaped episodes, few_shot_seg_cwt_amd/synthetic.py)",
-        "config": {"workload": (f"CWT training episode (do_epoch, batch_size=1, RCCL mean all-reduce of the "
-                                f"8.39 MB gradient bucket + nesterov SGD per step): " if args.train else
-                                f"CWT inference episode (validate_transformer, batch_size_val=1): ") +
-                               f"{'PASCAL split-0' if layers == 50 else 'COCO-20i split-0'} {shot}-shot "
-                               f"ResNet-{layers} PSPNet {S}x{S}, adapt_iter 200, heads 4",
-                   "image_size": S, "shot": shot, "layers": layers, "episodes_per_step_per_gpu": E,
-                   "parallelism": f"{world} episode-sharded replicas" + (f", {E} episodes in flight per GPU" if E > 1 else "")
-                   + (f", episode pipeline ({args.pipeline} extractor stream(s) beside the inner-loop / CWT stream: "
-                      "episode i+1's extractor pass overlaps episode i's inner loop, each episode alone)"
-                      if pipe is not None else "")},
+        **head,
         "roofline": {"bound": "hbm", "kernel": (ad_kernel + ", ...> (the 200-step inner loop, test.py:164-187; "
                                                 "the time-dominant kernel of the episode)"),
                      "achieved": round(ad_achieved, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
@@ -1034,9 +1102,7 @@ def main():
                           "gflop_reference_formulation_per_step": round(reference_cwt_flops(h_feat * h_feat) * E / 1e9, 2),
                           "note": "executed in the declared re-associated form (DESIGN.md §3, ~59 MFLOP of token work)"}},
         "tail_roofline": tail_roofline,
-        "iou_fg_timed": None if args.train else round(float((iu[0, 1] / iu[1, 1].clamp_min(1)).item()), 4),
         "sequential": seq,
-        "host_submit_ms_per_step": round((t_sub - t0) / args.steps * 1e3, 3),
         "batched_pipeline": pairs,
         "exact_fp32": exact_fp32,
         "bf16x3": bf16x3,

@@ -37,6 +37,41 @@ def test_bench_gpus1_single_process():
     assert lines == [{"rank": 0, "world": 1, "ranks_seen": 1}]
 
 
+def test_bench_profile_json_needs_full():
+    r = _run(["--gpus", "1", "--profile-json", os.devnull])
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs' writer: every tensor of a step's result as <name>.npy in float32 (float64
+    for integer and float64 tensors), non-tensors left out, an array above its share of the byte
+    budget stored as the same seeded sample every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    r = {"pred_q": torch.randn(1, 2, 9, 9, generator=g), "iut": torch.arange(6).view(1, 3, 2),
+         "ce": torch.randn(1, generator=g, dtype=torch.float64), "h": torch.randn(4, generator=g).half(),
+         "done": object()}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), r)
+    assert sorted(os.listdir(tmp_path / "a")) == ["ce.npy", "h.npy", "iut.npy", "pred_q.npy"]
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    assert {k: str(v.dtype) for k, v in got.items()} == {"pred_q": "float32", "iut": "float64", "ce": "float64",
+                                                         "h": "float32"}
+    for k, v in got.items():
+        assert list(v.shape) == shapes[k] == list(r[k].shape)
+        assert np.array_equal(v, r[k].double().numpy().astype(v.dtype))
+    # 4 arrays share a 1600-byte budget: 400 B each, so pred_q (648 B) is sampled to 100 floats
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1600)
+    s1 = bench.dump_outputs(str(tmp_path / "b"), r)
+    s2 = bench.dump_outputs(str(tmp_path / "c"), r)
+    assert s1 == s2 and s1["pred_q"] == [100] and s1["iut"] == [1, 3, 2]
+    b, c = np.load(tmp_path / "b" / "pred_q.npy"), np.load(tmp_path / "c" / "pred_q.npy")
+    assert np.array_equal(b, c) and np.isin(b, got["pred_q"]).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 1600 + 4 * 128
+
+
 def test_bench_train_two_ranks_cpu_standin():
     """bench.py --train past the launch check, world 2 on gloo: the CPU stand-in episode
     (CWT_BENCH_CPU_STANDIN) drives bench.py's own exchange (make_after: mean all-reduce of the

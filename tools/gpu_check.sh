@@ -16,6 +16,7 @@ rc=${PIPESTATUS[0]}
 echo "pytest rc=$rc"
 if [ $rc -gt 1 ]; then exit $rc; fi
 echo "== bench $(date +%T)"
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the per-launch records of --profile-json come from --full's extra episodes
 timeout -k 10 400 python -u bench.py --steps $STEPS --warmup 2 ${BENCH_ARGS:-} --profile-json gpurun_out/prof.json > gpurun_out/bench.json 2> >(tee gpurun_out/bench.err >&2)
 rc=$?
 echo "bench rc=$rc"
