@@ -14,6 +14,7 @@
 #include "../../include/cwt.h"
 #include "../../include/cwt_debug.h"
 #include "common.h"
+#include "conv_forms.h"
 #include "kernels.h"
 #include "tail_body.h"
 
@@ -323,6 +324,31 @@ static bool gemm_f32d_ok(int M, int N, int K, const void* A, const void* Bm, con
   return on && M >= 1 && K % 32 == 0 && N % 64 == 0 && N <= 8192 && (al & 15) == 0;
 }
 static int zero_line(cwt_ctx* ctx, const __bf16** out);
+
+static inline int conv_out_size(int in, int k, int stride, int pad, int dil) {
+  return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+}
+
+// A zeroed ConvSArgs with the conv's geometry, M and K set
+static ConvSArgs conv_s_geom(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dil) {
+  ConvSArgs a;
+  memset(&a, 0, sizeof(a));
+  a.N = N;
+  a.Hi = Hi;
+  a.Wi = Wi;
+  a.Ci = Ci;
+  a.Ho = conv_out_size(Hi, k, stride, pad, dil);
+  a.Wo = conv_out_size(Wi, k, stride, pad, dil);
+  a.Co = Co;
+  a.kh = a.kw = k;
+  a.stride = stride;
+  a.pad = pad;
+  a.dil = dil;
+  a.M = N * a.Ho * a.Wo;
+  a.K = k * k * Ci;
+  return a;
+}
+
 static int gemm_f32d(cwt_ctx* ctx, const float* A, const float* Bm, int M, int N, int K, float* Cm, const float* bias,
                      const float* res, int res_ld, hipStream_t st, int relu = 0) {
   const bool fresh = ctx->ws.find("gemm.one") == ctx->ws.end();
@@ -336,11 +362,10 @@ static int gemm_f32d(cwt_ctx* ctx, const float* A, const float* Bm, int M, int N
     CWT_HIP(hipMemsetD32((hipDeviceptr_t)one, 0x3f800000u, 8192));  // 1.0f
     CWT_HIP(hipMemset(zer, 0, 8192 * 4));
   }
-  const ConvPlan pl = plan_conv_f32d(M, N, K);
+  const ConvPlan pl = plan_conv_s(0, M, N, K);
   const size_t part_floats = pl.nsplit > 1 ? (size_t)pl.nsplit * M * N : 1;
   if ((rc = ensure_ws(ctx, "gemm.part", part_floats * 4, &part))) return rc;
-  ConvSArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvSArgs a = conv_s_geom(1, M, 1, K, N, 1, 1, 0, 1);  // a 1x1 conv over M pixels
   a.xs = (const __bf16*)A;
   a.ws = (const __bf16*)Bm;
   a.zero = zero;
@@ -350,18 +375,6 @@ static int gemm_f32d(cwt_ctx* ctx, const float* A, const float* Bm, int M, int N
   a.res_ld = res_ld;
   a.y = Cm;
   a.y_ld = N;
-  a.N = 1;
-  a.Hi = M;
-  a.Wi = 1;
-  a.Ci = K;
-  a.Ho = M;
-  a.Wo = 1;
-  a.Co = N;
-  a.kh = a.kw = 1;
-  a.stride = 1;
-  a.dil = 1;
-  a.M = M;
-  a.K = K;
   a.relu = relu;
   return launch_conv_x3s(a, pl, 0, (float*)part, part_floats, st, 0);
 }
@@ -677,8 +690,8 @@ static ConvArgs make_args(const ConvCall& c) {
   a.Wi = c.Wi;
   a.Ci = L.Ci;
   a.x_ld = c.x_ld;
-  a.Ho = (c.Hi + 2 * L.pad - L.dil * (L.k - 1) - 1) / L.stride + 1;
-  a.Wo = (c.Wi + 2 * L.pad - L.dil * (L.k - 1) - 1) / L.stride + 1;
+  a.Ho = conv_out_size(c.Hi, L.k, L.stride, L.pad, L.dil);
+  a.Wo = conv_out_size(c.Wi, L.k, L.stride, L.pad, L.dil);
   a.Co = L.Co;
   a.kh = a.kw = L.k;
   a.stride = L.stride;
@@ -705,6 +718,24 @@ static int wino_tile_default(int Ci, int Co, int d, int Ho) {
   return Ci >= 256 ? 2 : 0;
 }
 
+// The debug entry points' forced form: bm = 1000 * variant + rows (cwt_debug.h) and bn must name a
+// row of the family's form table (conv_forms.h); a timing-study form's fixed tile replaces the one
+// named beside it (the grid must be the kernel's).
+static int force_conv_form(int prec, int bm, int bn, int Co, ConvPlan* p) {
+  const int var = bm / 1000;
+  bm %= 1000;
+  CWT_CHECK(find_conv_form(prec, bm, bn, 0),
+            "tile must be one of 256x256, 256x128, 128x256, 128x128, 128x64, 64x128, 64x64");
+  const ConvForm* f = fixed_tile_form(prec, var);
+  if (!f) f = find_conv_form(prec, bm, bn, var);
+  CWT_CHECK(f, "no such conv form: the variant does not exist on this tile (conv_forms.h)");
+  CWT_CHECK(Co % f->bn == 0, "Co % bn");
+  p->bm = f->bm;
+  p->bn = f->bn;
+  p->var = var;
+  return 0;
+}
+
 // One stride-1 3x3 conv (dilation d = padding) in the Winograd form F(m x m, 3x3) on the x6
 // matrix-core arithmetic (wino.hip): input transform -> P = (m+2)^2 batched GEMMs
 // (conv_igemm_x6, batch P) -> output transform with the conv's BN / residual / ReLU.  us / ul: the
@@ -720,6 +751,8 @@ static int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int 
   void *V, *Mb;
   const __bf16* zero = nullptr;
   int rc;
+  ConvPlan p = plan_conv_s(6, (int)g.T, Co, Ci, g.P);
+  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &p))) return rc;
   if ((rc = ensure_ws(ctx, "wino.V", (size_t)g.P * g.T * Ci * 4, &V)) ||
       (rc = ensure_ws(ctx, "wino.M", (size_t)g.P * g.T * Co * 4, &Mb)) || (rc = zero_line(ctx, &zero)))
     return rc;
@@ -734,39 +767,18 @@ static int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int 
   rc = launch_wino_in(x, g, Ci, (float*)V, st);
   pin.end();
   if (rc) return rc;
-  ConvSArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvSArgs a = conv_s_geom(1, (int)g.T, 1, Ci, Co, 1, 1, 0, 1);  // each GEMM: a 1x1 conv over the T tiles
   a.xs = (const __bf16*)V;
   a.ws = us;
   a.ws_lo = ul;
   a.zero = zero;
   a.scale = scale;
   a.shift = shift;
-  a.N = 1;
-  a.Hi = (int)g.T;
-  a.Wi = 1;
-  a.Ci = Ci;
-  a.Ho = (int)g.T;
-  a.Wo = 1;
-  a.Co = Co;
-  a.kh = a.kw = 1;
-  a.stride = 1;
-  a.pad = 0;
-  a.dil = 1;
-  a.M = (int)g.T;
-  a.K = Ci;
   a.part = (float*)Mb;
   a.batch = g.P;
   a.xs_bstride = g.T * Ci * 4;
   a.ws_bstride = (long)Co * Ci * 2;
   a.wl_bstride = (long)Co * Ci;
-  ConvPlan p = plan_conv_x6_batched(a.M, Co, Ci, g.P);
-  if (bm > 0) {
-    p.var = bm / 1000;
-    p.bm = bm % 1000;
-    p.bn = bn;
-    if (Co % p.bn) return fail(CWT_EARG, "winograd GEMM tile: Co % bn");
-  }
   // the batched GEMMs are the stage-7 (F(2x2)) / stage-8 (F(4x4)) instantiations, the
   // bottleneck's (stage 6) its own: their own rocprofv3 statistics
   Prof pg(ctx, st, "wino_gemm " + std::to_string(Ci) + "x" + std::to_string(Co) + "@" + std::to_string(H),
@@ -903,9 +915,7 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
   for (auto& c : calls) {
     ConvArgs a = make_args(c);
     if (b16 && !c.L->w_b) return fail(CWT_ESTATE, "bf16 conv weights missing (Ci % 64 != 0)");
-    ConvPlan pl = b16 ? plan_conv_b16(a.M, a.Co, a.K) : conv_split ? plan_conv_x3s(a.M, a.Co, a.K)
-                  : x6 ? plan_conv_x6(a.M, a.Co, a.K) : f32d ? plan_conv_f32d(a.M, a.Co, a.K)
-                                                         : plan_conv(a.M, a.Co, a.K);
+    ConvPlan pl = dma ? plan_conv_s(prec, a.M, a.Co, a.K) : plan_conv(a.M, a.Co, a.K);
     plans.push_back(pl);
     if (pl.nsplit > 1) part_floats = std::max(part_floats, (size_t)pl.nsplit * a.M * a.Co);
   }
@@ -979,7 +989,7 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
     // the Winograd form's record names its batched GEMM's plan; its FLOPs stay the direct conv's
     // (algorithmic: the roofline prices the conv, not the form that computes it)
     const WinoGeom wg = wino_geom(a.N, a.Hi, a.Wi, a.dil, wm ? wm : 2);
-    const ConvPlan pl = wino ? plan_conv_x6_batched((int)wg.T, a.Co, a.Ci, wg.P) : plans[i];
+    const ConvPlan pl = wino ? plan_conv_s(6, (int)wg.T, a.Co, a.Ci, wg.P) : plans[i];
     const double flops = 2.0 * a.M * a.Co * a.K;
     // algorithmic bytes: every operand once; 4 B per element (fp32 or the bf16x3 S-layout),
     // 2 B for the bf16 stack's activations and weights (its fp32 bottleneck output: 4 B)
@@ -1003,8 +1013,7 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
                         wm == 4 ? c.L->wino4_l : c.L->wino_l, a.scale, a.shift, a.res, c.res_ld, a.relu, c.y, c.y_ld,
                         c.y_off, c.stage, st);
     } else if (dma) {
-      ConvSArgs sa;
-      memset(&sa, 0, sizeof(sa));
+      ConvSArgs sa = conv_s_geom(a.N, a.Hi, a.Wi, a.Ci, a.Co, a.kh, a.stride, a.pad, a.dil);
       const ConvCall& c = calls[i];
       sa.xs = (const __bf16*)c.x;  // (f32d: the fp32 NHWC map, the same 128-B line geometry)
       sa.ws = b16 ? c.L->w_b : f32d ? (const __bf16*)c.L->w : c.L->w_s;  // x6: hi | mid (+ ws_lo)
@@ -1023,20 +1032,6 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
         sa.res_s = (const __bf16*)a.res;
       }
       sa.relu = a.relu;
-      sa.N = a.N;
-      sa.Hi = a.Hi;
-      sa.Wi = a.Wi;
-      sa.Ci = a.Ci;
-      sa.Ho = a.Ho;
-      sa.Wo = a.Wo;
-      sa.Co = a.Co;
-      sa.kh = a.kh;
-      sa.kw = a.kw;
-      sa.stride = a.stride;
-      sa.pad = a.pad;
-      sa.dil = a.dil;
-      sa.M = a.M;
-      sa.K = a.K;
       r = launch_conv_x3s(sa, pl, c.stage, PART, part_floats, st, prec);
     } else {
       r = launch_conv(a, pl, calls[i].stage, PART, part_floats, st);
@@ -2683,10 +2678,11 @@ static int debug_conv_s(cwt_ctx* ctx, int prec, const void* xs, int N, int Hi, i
   const int kb = prec == 1 ? 64 : 32;
   CWT_CHECK(Ci % kb == 0 && Co % 64 == 0, prec == 1 ? "need Ci%64==0, Co%64==0" : "need Ci%32==0, Co%64==0");
   CWT_CHECK(!y || (y_ld >= y_off + Co && y_ld % 4 == 0 && y_off % 4 == 0), "bad y stride");
-  CWT_HIP(hipSetDevice(ctx->device));
-  ConvSArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvSArgs a = conv_s_geom(N, Hi, Wi, Ci, Co, k, stride, pad, dil);
   int rc;
+  ConvPlan p = plan_conv_s(prec, a.M, a.Co, a.K);
+  if (bm > 0 && (rc = force_conv_form(prec, bm, bn, Co, &p))) return rc;  // before any device call
+  CWT_HIP(hipSetDevice(ctx->device));
   if ((rc = zero_line(ctx, &a.zero))) return rc;
   a.xs = (const __bf16*)xs;
   a.ws = (const __bf16*)ws;
@@ -2700,45 +2696,6 @@ static int debug_conv_s(cwt_ctx* ctx, int prec, const void* xs, int N, int Hi, i
   a.y_ld = y_ld;
   a.y_off = y_off;
   a.ys = (__bf16*)ys;
-  a.N = N;
-  a.Hi = Hi;
-  a.Wi = Wi;
-  a.Ci = Ci;
-  a.Co = Co;
-  a.kh = a.kw = k;
-  a.stride = stride;
-  a.pad = pad;
-  a.dil = dil;
-  a.Ho = (Hi + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-  a.Wo = (Wi + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-  a.M = N * a.Ho * a.Wo;
-  a.K = k * k * Ci;
-  ConvPlan p = prec == 1   ? plan_conv_b16(a.M, a.Co, a.K)
-               : prec == 0 ? plan_conv_f32d(a.M, a.Co, a.K)
-               : prec == 6 ? plan_conv_x6(a.M, a.Co, a.K)
-                           : plan_conv_x3s(a.M, a.Co, a.K);
-  if (bm > 0) {
-    const int var = bm / 1000;  // bm = 1000 * variant + rows (cwt_debug.h)
-    bm %= 1000;
-    CWT_CHECK((bm == 256 && (bn == 256 || bn == 128)) || (bm == 128 && (bn == 256 || bn == 128 || bn == 64)) ||
-                  (bm == 64 && (bn == 128 || bn == 64)),
-              "tile must be one of 256x256, 256x128, 128x256, 128x128, 128x64, 64x128, 64x64");
-    const bool x6_var = prec == 6 && ((var == 3 && (bm >= 128 && bn >= 128)) || (var == 5 && bm == 128 && bn == 128) ||
-                                      ((var == 3 || var == 5) && bm == 64 && bn == 128) ||
-                                      ((var == 3 || var == 5) && bm == 128 && bn == 64) || (var == 3 && bm == 64 && bn == 64) ||
-                                      ((var == 12 || (var >= 14 && var <= 18)) && bm == 128 && bn == 128) ||
-                                      (var == 13 && bm == 256 && bn == 256));
-    CWT_CHECK((var >= 0 && var <= 2) || (var == 4 && bm == 128 && bn == 128) || (var >= 8 && var <= 11) || x6_var,
-              "variant must be 0, 1, 2, 4 (128x128 only), 8 .. 11 (timing study), or for x6 3 (tiles >= 128x128) "
-              "and 5 (128x128)");
-    if (var >= 8 && var <= 11 && !x6_var) {  // the timing-study kernels have fixed tiles: the grid must be theirs
-      bm = bn = var < 10 ? 64 : 128;
-    }
-    CWT_CHECK(Co % bn == 0, "Co % bn");
-    p.bm = bm;
-    p.bn = bn;
-    p.var = var;
-  }
   if (nsplit > 0) {
     const int kt = a.K / kb;
     p.kt_per_split = cdiv(kt, nsplit);
@@ -2796,6 +2753,27 @@ int cwt_debug_conv_x6(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int C
                       relu, y, y_ld, y_off, nullptr, bm, bn, nsplit, stream);
 }
 
+int cwt_debug_conv_form(int prec, int bm, int bn, int var, int* out4) {
+  CWT_CHECK(out4, "out4 is NULL");
+  const ConvForm* f = find_conv_form(prec, bm, bn, var);
+  if (!f) return fail(CWT_EARG, "no such conv form (conv_forms.h)");
+  out4[0] = f->waves_m;
+  out4[1] = f->waves_n;
+  out4[2] = f->nstg;
+  out4[3] = f->pf;
+  return 0;
+}
+
+int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5) {
+  CWT_CHECK(out5 && M > 0 && Co > 0 && K > 0 && batch >= 0, "bad arguments");
+  CWT_CHECK(prec == 0 || prec == 1 || prec == 3 || prec == 6, "prec must be 0, 1, 3 or 6");
+  const ConvPlan p = plan_conv_s(prec, M, Co, K, batch);
+  const int v[5] = {p.bm, p.bn, p.var, p.nsplit, p.kt_per_split};
+  std::copy(v, v + 5, out5);
+  if (!find_conv_form(prec, p.bm, p.bn, p.var)) return fail(CWT_EARG, "the plan's form is no such conv form");
+  return 0;
+}
+
 int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
                        const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
@@ -2807,14 +2785,14 @@ int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int 
   CWT_CHECK(k == 3 && stride == 1 && pad == dil && dil >= 1, "winograd form: 3x3, stride 1, padding = dilation");
   CWT_CHECK(Ci % 32 == 0 && Co % 64 == 0 && N >= 1 && Hi >= 1 && Wi >= 1, "need Ci % 32 == 0, Co % 64 == 0");
   CWT_CHECK(y_ld >= y_off + Co && y_ld % 4 == 0 && y_off % 4 == 0 && (!res || res_ld % 4 == 0), "bad strides");
-  CWT_CHECK(bm == 0 || ((bm % 1000 == 256 || bm % 1000 == 128 || bm % 1000 == 64) && (bn == 256 || bn == 128 || bn == 64)),
-            "bad tile");
+  int rc;
+  ConvPlan named;  // refused here, before the weights' transform is launched (run_wino_conv forces it)
+  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &named))) return rc;
   CWT_HIP(hipSetDevice(ctx->device));
   const hipStream_t st = (hipStream_t)stream;
   const int P = (m + 2) * (m + 2);
   const size_t n = (size_t)P * Co * Ci;
   void *U, *us, *ul;
-  int rc;
   if ((rc = ensure_ws(ctx, "dbg.wU", n * 4, &U)) || (rc = ensure_ws(ctx, "dbg.wUs", n * 4, &us)) ||
       (rc = ensure_ws(ctx, "dbg.wUl", n * 2, &ul)))
     return rc;

@@ -32,7 +32,11 @@
 // so a K-tile is 64 deep and its two 32-deep halves (chunks 0-3 and 4-7 of the row, where
 // PREC 3 keeps hi and lo) take one MFMA each.  fp32 accumulation; BN, residual and ReLU in
 // fp32; outputs rounded to bf16 (fp32 for the last conv, whose output is the feature map).
+#include <algorithm>
+#include <iterator>
+
 #include "conv_body.h"
+#include "conv_forms.h"
 
 namespace cwt {
 // STAGE only names the instantiation (rocprofv3 reports the conv stack by stage).
@@ -158,71 +162,67 @@ int launch_unsplit_act(const __bf16* s, long P, int C, float* out, int ld, hipSt
   return 0;
 }
 
-// plan.var: 0 = the base loop; 1 = fragment prefetch (PF), same waves; 2 = PF with 8 waves
-// (two per SIMD) on the 128- and 64-row tiles; 4 = 128x128 with a 2-stage ring (64 KB: two
-// workgroups per CU).  Deeper rings (one workgroup per CU, 4-5 tiles in flight) measured no
-// faster: a workgroup's LDS-DMA intake, not its bytes in flight, is the limit.  256x256 has no PF form: its second fragment
-// set does not fit the 256 VGPRs of a wave at two waves per SIMD.
-#define CWT_TILE_LAUNCH(KERNEL)                                                                                  \
-  template <int STAGE>                                                                                       \
-  static void launch_tiles_##KERNEL(const ConvSArgs& a, const ConvPlan& p, dim3 grid, hipStream_t st) {      \
-    const int v = p.var;                                                                                     \
-    if (v >= 8) { /* timing study (cwt_debug_conv_s only): 8/9 base 64x64 w/o MFMA / w/o DMA,            */ \
-      /* 10/11 the 8-wave prefetch 128x128 w/o MFMA / w/o DMA                                              */ \
-      if (v == 8) hipLaunchKernelGGL((KERNEL<64, 64, 2, 2, 4, 0, 2>), grid, dim3(256), 0, st, a);           \
-      else if (v == 9) hipLaunchKernelGGL((KERNEL<64, 64, 2, 2, 4, 0, 4>), grid, dim3(256), 0, st, a);      \
-      else if (v == 10) hipLaunchKernelGGL((KERNEL<128, 128, 2, 4, 3, 0, 3>), grid, dim3(512), 0, st, a);   \
-      else hipLaunchKernelGGL((KERNEL<128, 128, 2, 4, 3, 0, 5>), grid, dim3(512), 0, st, a);                \
-      return;                                                                                                \
-    }                                                                                                        \
-    if (p.bm == 256 && p.bn == 256) {                                                                        \
-      hipLaunchKernelGGL((KERNEL<256, 256, 2, 4, 2, STAGE, 0>), grid, dim3(512), 0, st, a); /* PF: no VGPRs */ \
-    } else if (p.bm == 256 && p.bn == 128) {                                                                 \
-      if (v) hipLaunchKernelGGL((KERNEL<256, 128, 4, 2, 3, STAGE, 1>), grid, dim3(512), 0, st, a);           \
-      else hipLaunchKernelGGL((KERNEL<256, 128, 4, 2, 3, STAGE, 0>), grid, dim3(512), 0, st, a);             \
-    } else if (p.bm == 128 && p.bn == 256) {                                                                 \
-      if (v) hipLaunchKernelGGL((KERNEL<128, 256, 2, 4, 3, STAGE, 1>), grid, dim3(512), 0, st, a);           \
-      else hipLaunchKernelGGL((KERNEL<128, 256, 2, 4, 3, STAGE, 0>), grid, dim3(512), 0, st, a);             \
-    } else if (p.bm == 128 && p.bn == 128) {                                                                 \
-      if (v == 4) hipLaunchKernelGGL((KERNEL<128, 128, 2, 2, 2, STAGE, 0>), grid, dim3(256), 0, st, a);      \
-      else if (v == 2) hipLaunchKernelGGL((KERNEL<128, 128, 2, 4, 3, STAGE, 1>), grid, dim3(512), 0, st, a); \
-      else if (v) hipLaunchKernelGGL((KERNEL<128, 128, 2, 2, 3, STAGE, 1>), grid, dim3(256), 0, st, a);      \
-      else hipLaunchKernelGGL((KERNEL<128, 128, 2, 2, 3, STAGE, 0>), grid, dim3(256), 0, st, a);             \
-    } else if (p.bm == 128 && p.bn == 64) {                                                                  \
-      if (v == 2) hipLaunchKernelGGL((KERNEL<128, 64, 4, 2, 3, STAGE, 1>), grid, dim3(512), 0, st, a);  \
-      else if (v) hipLaunchKernelGGL((KERNEL<128, 64, 2, 2, 3, STAGE, 1>), grid, dim3(256), 0, st, a);       \
-      else hipLaunchKernelGGL((KERNEL<128, 64, 2, 2, 3, STAGE, 0>), grid, dim3(256), 0, st, a);              \
-    } else if (p.bm == 64 && p.bn == 128) {                                                                  \
-      if (v == 2) hipLaunchKernelGGL((KERNEL<64, 128, 2, 4, 3, STAGE, 1>), grid, dim3(512), 0, st, a);  \
-      else if (v) hipLaunchKernelGGL((KERNEL<64, 128, 2, 2, 3, STAGE, 1>), grid, dim3(256), 0, st, a);       \
-      else hipLaunchKernelGGL((KERNEL<64, 128, 2, 2, 3, STAGE, 0>), grid, dim3(256), 0, st, a);              \
-    } else {                                                                                                 \
-      if (v == 2) hipLaunchKernelGGL((KERNEL<64, 64, 2, 4, 4, STAGE, 1>), grid, dim3(512), 0, st, a);   \
-      else if (v) hipLaunchKernelGGL((KERNEL<64, 64, 2, 2, 4, STAGE, 1>), grid, dim3(256), 0, st, a);        \
-      else hipLaunchKernelGGL((KERNEL<64, 64, 2, 2, 4, STAGE, 0>), grid, dim3(256), 0, st, a);               \
-    }                                                                                                        \
-  }
-CWT_TILE_LAUNCH(conv_igemm_x3s)
-CWT_TILE_LAUNCH(conv_igemm_b16)
-CWT_TILE_LAUNCH(conv_igemm_f32d)
-#undef CWT_TILE_LAUNCH
+// The forms (plan.var on each tile) and their launcher: conv_forms.h
+CWT_CONV_FAMILY(FamX3s, conv_igemm_x3s, false, true);
+CWT_CONV_FAMILY(FamB16, conv_igemm_b16, false, true);
+CWT_CONV_FAMILY(FamF32d, conv_igemm_f32d, false, true);
 
-struct MeasuredPlanS {
-  int M, Co, K, bm, bn, nsplit, var;  // var: main-loop variant (launch_tiles_*; 0 where a line omits it)
+#define CWT_ROW(BM, BN, VAR, WM, WN, NS, PF, FIXED) {BM, BN, VAR, WM, WN, NS, PF, FIXED != 0, -1},
+#define CWT_ALIAS(BM, BN, VAR, TARGET) {BM, BN, VAR, 0, 0, 0, 0, false, TARGET},
+static constexpr ConvForm kConvForms[] = {CWT_CONV_FORMS(CWT_ROW, CWT_ALIAS)};
+static constexpr ConvForm kConvFormsX6[] = {CWT_CONV_FORMS(CWT_ROW, CWT_ALIAS) CWT_CONV_FORMS_X6(CWT_ROW, CWT_ALIAS)};
+#undef CWT_ROW
+#undef CWT_ALIAS
+
+template <class Pred>
+static const ConvForm* find_form_if(int prec, Pred pred) {
+  if (prec != 0 && prec != 1 && prec != 3 && prec != 6) return nullptr;
+  const ConvForm* t = prec == 6 ? kConvFormsX6 : kConvForms;
+  const size_t n = prec == 6 ? std::size(kConvFormsX6) : std::size(kConvForms);
+  const ConvForm* e = std::find_if(t, t + n, pred);
+  return e == t + n ? nullptr : e;
+}
+
+const ConvForm* find_conv_form(int prec, int bm, int bn, int var) {
+  const auto row = [&](int v) {
+    return find_form_if(prec, [=](const ConvForm& f) { return f.bm == bm && f.bn == bn && f.var == v; });
+  };
+  const ConvForm* f = row(var);
+  return f && f->alias >= 0 ? row(f->alias) : f;
+}
+
+const ConvForm* fixed_tile_form(int prec, int var) {
+  return find_form_if(prec, [=](const ConvForm& f) { return f.fixed_tile && f.var == var; });
+}
+
+// One measured row: batch 0 for a direct conv's GEMM, else the Winograd form's GEMM count (16 or
+// 36) with M its tiles; var the form on the tile (conv_forms.h; 0 where a line omits it)
+struct MeasuredPlan {
+  int M, Co, K, bm, bn, nsplit, var, batch = 0;
 };
-static const MeasuredPlanS kMeasuredPlansS[] = {
+// The sweeps' tables (tools/gen_plan_table.py from tools/conv_s_sweep.py --prec P on the MI355X)
+static const MeasuredPlan kMeasuredPlansS[] = {
 #include "conv_plans_x3s.inc"
-};
+    {}};
+static const MeasuredPlan kMeasuredPlansB16[] = {
+#include "conv_plans_b16.inc"
+    {}};
+static const MeasuredPlan kMeasuredPlansF32D[] = {
+#include "conv_plans_f32d.inc"
+    {}};
+static const MeasuredPlan kMeasuredPlansX6[] = {
+#include "conv_plans_x6.inc"
+    {}};
 
-// The measured plan for this GEMM shape if the sweep found one (conv_plans_x3s.inc, made by
-// tools/gen_plan_table.py --x3s from tools/conv_s_sweep.py on the MI355X), else the largest
-// tile giving >= kMinWG workgroups, splitting K by powers of two (>= 8 K-tiles per split)
-// where the output grid is too small.
+// the heuristics' candidates, largest first
+static const int kPlanTiles[7][2] = {{256, 256}, {256, 128}, {128, 256}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};
+
+// The largest tile giving >= kMinWG workgroups, splitting K by powers of two (>= 8 K-tiles per
+// split) where the output grid is too small.
 ConvPlan plan_heuristic_s(int M, int Co, int ktiles) {
   constexpr long kMinWG = 200;
-  static const int cand[7][2] = {{256, 256}, {256, 128}, {128, 256}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};
   ConvPlan best;
-  for (auto& c : cand) {
+  for (auto& c : kPlanTiles) {
     if (Co % c[1] != 0) continue;
     const long tiles = (long)cdiv(M, c[0]) * (Co / c[1]);
     int ks = 1;
@@ -238,31 +238,31 @@ ConvPlan plan_heuristic_s(int M, int Co, int ktiles) {
   return best;
 }
 
-ConvPlan plan_conv_x3s(int M, int Co, int K) {
-  const int ktiles = K / 32;
-  for (const MeasuredPlanS& e : kMeasuredPlansS)
-    if (e.M == M && e.Co == Co && e.K == K && Co % e.bn == 0) {
-      ConvPlan p;
-      p.bm = e.bm;
-      p.bn = e.bn;
-      p.var = e.var;
-      p.kt_per_split = cdiv(ktiles, e.nsplit);
-      p.nsplit = cdiv(ktiles, p.kt_per_split);
-      return p;
-    }
-  return plan_heuristic_s(M, Co, ktiles);
+// The Winograd forms' batched GEMMs [M = tiles][K = Ci] x [Ci][Co] (batch 16 or 36): the largest
+// tile giving >= 200 workgroups over the whole batch, no split-K
+static ConvPlan plan_heuristic_batched(int M, int Co, int ktiles, int batch) {
+  ConvPlan best;
+  for (auto& c : kPlanTiles) {
+    if (Co % c[1] != 0) continue;
+    ConvPlan p;
+    p.bm = c[0];
+    p.bn = c[1];
+    p.kt_per_split = ktiles;
+    p.nsplit = 1;
+    best = p;
+    if ((long)cdiv(M, c[0]) * (Co / c[1]) * batch >= 200) return p;
+  }
+  return best;
 }
 
-static const MeasuredPlanS kMeasuredPlansB16[] = {
-#include "conv_plans_b16.inc"
-};
-
-// Plain bf16: 64-deep K-tiles; its own measured table (conv_plans_b16.inc, tools/conv_s_sweep.py
-// --prec 1), else the heuristic.
-ConvPlan plan_conv_b16(int M, int Co, int K) {
-  const int ktiles = K / 64;
-  for (const MeasuredPlanS& e : kMeasuredPlansB16)
-    if (e.M == M && e.Co == Co && e.K == K && Co % e.bn == 0) {
+// The measured plan of this GEMM shape if the sweep found one (a batched GEMM's: split-free rows
+// only), else the heuristic's.  kdepth: the K-tile's depth.
+template <size_t N>
+static ConvPlan plan_from_table(const MeasuredPlan (&table)[N], int M, int Co, int K, int kdepth, int batch) {
+  const int ktiles = K / kdepth;
+  for (const MeasuredPlan& e : table)
+    if (e.batch == batch && e.M == M && e.Co == Co && e.K == K && e.bn > 0 && Co % e.bn == 0 &&
+        (batch == 0 || e.nsplit == 1)) {
       ConvPlan p;
       p.bm = e.bm;
       p.bn = e.bn;
@@ -271,28 +271,16 @@ ConvPlan plan_conv_b16(int M, int Co, int K) {
       p.nsplit = cdiv(ktiles, p.kt_per_split);
       return p;
     }
-  return plan_heuristic_s(M, Co, ktiles);
+  return batch ? plan_heuristic_batched(M, Co, ktiles, batch) : plan_heuristic_s(M, Co, ktiles);
 }
 
-static const MeasuredPlanS kMeasuredPlansF32D[] = {
-#include "conv_plans_f32d.inc"
-    {0, 0, 0, 0, 0, 0, 0}};
-
-// Exact fp32 on the LDS-DMA body: 32-deep K-tiles; its own measured table
-// (conv_plans_f32d.inc, tools/conv_s_sweep.py --prec 0), else the heuristic.
-ConvPlan plan_conv_f32d(int M, int Co, int K) {
-  const int ktiles = K / 32;
-  for (const MeasuredPlanS& e : kMeasuredPlansF32D)
-    if (e.M == M && e.Co == Co && e.K == K && e.bn > 0 && Co % e.bn == 0) {
-      ConvPlan p;
-      p.bm = e.bm;
-      p.bn = e.bn;
-      p.var = e.var;
-      p.kt_per_split = cdiv(ktiles, e.nsplit);
-      p.nsplit = cdiv(ktiles, p.kt_per_split);
-      return p;
-    }
-  return plan_heuristic_s(M, Co, ktiles);
+ConvPlan plan_conv_s(int prec, int M, int Co, int K, int batch) {
+  switch (prec) {
+    case 0: return plan_from_table(kMeasuredPlansF32D, M, Co, K, 32, batch);
+    case 1: return plan_from_table(kMeasuredPlansB16, M, Co, K, 64, batch);  // plain bf16: 64-deep K-tiles
+    case 6: return plan_from_table(kMeasuredPlansX6, M, Co, K, 32, batch);
+    default: return plan_from_table(kMeasuredPlansS, M, Co, K, 32, batch);
+  }
 }
 
 template <int PREC>
@@ -309,11 +297,13 @@ static void launch_splitk_s(const ConvSArgs& a, int nsplit, hipStream_t st) {
 }
 
 // prec 3: bf16x3 over S-layout operands; prec 1: plain bf16 (NHWC bf16 activations, weights in
-// 64-channel-block order, plan_conv_b16)
+// 64-channel-block order)
 int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
                     hipStream_t st, int prec) {
   if (prec != 0 && prec != 1 && prec != 3 && prec != 6)
     return fail(CWT_EARG, "conv precision must be 3 (bf16x3), 1 (bf16), 0 (exact fp32) or 6 (bf16x6)");
+  const ConvForm* form = find_conv_form(prec, p.bm, p.bn, p.var);
+  if (!form) return fail(CWT_EARG, "no such conv form (conv_forms.h)");
   const bool batched = prec == 6 && a.batch > 1;
   if ((prec == 0 || prec == 6) && (a.ys || a.res_s || (!a.y && !batched)))
     return fail(CWT_EARG, "fp32-operand conv: fp32 output and residual only");
@@ -340,39 +330,19 @@ int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, s
     main.part = nullptr;
   }
   dim3 grid(cdiv(a.M, p.bm), a.Co / p.bn, nsplit * (batched ? a.batch : 1));
-  if (prec == 6) {
-    launch_tiles_x6(stage, main, p, grid, st);
-  } else if (prec == 0) {
-    switch (stage) {
-      case 0: launch_tiles_conv_igemm_f32d<0>(main, p, grid, st); break;
-      case 1: launch_tiles_conv_igemm_f32d<1>(main, p, grid, st); break;
-      case 2: launch_tiles_conv_igemm_f32d<2>(main, p, grid, st); break;
-      case 3: launch_tiles_conv_igemm_f32d<3>(main, p, grid, st); break;
-      case 4: launch_tiles_conv_igemm_f32d<4>(main, p, grid, st); break;
-      case 5: launch_tiles_conv_igemm_f32d<5>(main, p, grid, st); break;
-      default: launch_tiles_conv_igemm_f32d<6>(main, p, grid, st); break;
-    }
-  } else if (prec == 1) {
-    switch (stage) {
-      case 0: launch_tiles_conv_igemm_b16<0>(main, p, grid, st); break;
-      case 1: launch_tiles_conv_igemm_b16<1>(main, p, grid, st); break;
-      case 2: launch_tiles_conv_igemm_b16<2>(main, p, grid, st); break;
-      case 3: launch_tiles_conv_igemm_b16<3>(main, p, grid, st); break;
-      case 4: launch_tiles_conv_igemm_b16<4>(main, p, grid, st); break;
-      case 5: launch_tiles_conv_igemm_b16<5>(main, p, grid, st); break;
-      default: launch_tiles_conv_igemm_b16<6>(main, p, grid, st); break;
-    }
-  } else {
-    switch (stage) {
-      case 0: launch_tiles_conv_igemm_x3s<0>(main, p, grid, st); break;
-      case 1: launch_tiles_conv_igemm_x3s<1>(main, p, grid, st); break;
-      case 2: launch_tiles_conv_igemm_x3s<2>(main, p, grid, st); break;
-      case 3: launch_tiles_conv_igemm_x3s<3>(main, p, grid, st); break;
-      case 4: launch_tiles_conv_igemm_x3s<4>(main, p, grid, st); break;
-      case 5: launch_tiles_conv_igemm_x3s<5>(main, p, grid, st); break;
-      default: launch_tiles_conv_igemm_x3s<6>(main, p, grid, st); break;
-    }
-  }
+  ConvPlan row = p;
+  row.var = form->var;  // an alias names its target
+  const auto launch = [&](auto fam) {
+    with_stage<6>(stage, [&](auto s) { launch_form<decltype(fam), decltype(s)::value>(row, main, grid, st); });
+  };
+  if (prec == 6)
+    launch_tiles_x6(stage, main, row, grid, st);
+  else if (prec == 0)
+    launch(FamF32d{});
+  else if (prec == 1)
+    launch(FamB16{});
+  else
+    launch(FamX3s{});
   CWT_LAUNCH_CHECK();
   if (nsplit > 1 && !batched) {
     main.part = part_ws;

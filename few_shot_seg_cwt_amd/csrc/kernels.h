@@ -113,18 +113,15 @@ __device__ __forceinline__ void conv_store_fragment(const ConvArgs& a, const f32
 
 struct ConvPlan {
   int bm = 128, bn = 128, kt_per_split = 1, nsplit = 1;
-  int var = 0;  // S-layout convs: 0 base main loop, 1 fragment prefetch, 2 prefetch with 8 waves (conv_x3s.hip)
+  int var = 0;  // LDS-DMA convs: the kernel form on the tile (conv_forms.h)
 };
 
 ConvPlan plan_conv(int M, int Co, int K);
 int launch_conv(ConvArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats, hipStream_t st);
 int launch_splitk_epilogue(const ConvArgs& a, int nsplit, hipStream_t st);
-// split-activation variant (conv_x3s.hip)
-ConvPlan plan_conv_x3s(int M, int Co, int K);
-ConvPlan plan_conv_b16(int M, int Co, int K);
-ConvPlan plan_conv_f32d(int M, int Co, int K);
-ConvPlan plan_conv_x6(int M, int Co, int K);
-ConvPlan plan_conv_x6_batched(int M, int Co, int K, int batch);  // the Winograd forms' GEMMs
+// The LDS-DMA convs (conv_x3s.hip; prec as launch_conv_x3s): the measured plan of the GEMM shape,
+// else the heuristic's.  batch: 0 a direct conv, else the Winograd form's GEMM count, M its tiles
+ConvPlan plan_conv_s(int prec, int M, int Co, int K, int batch = 0);
 // Winograd F(2x2, 3x3) and F(4x4, 3x3) for the x6 path's stride-1 3x3 convs (wino.hip)
 struct WinoGeom {
   int N, H, W, d;  // image, dilation (= padding)

@@ -34,9 +34,9 @@ int cwt_debug_conv(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, 
  * K = k*k*Ci in the library's K order.  cwt_debug_conv_s: one conv on S-layout input and
  * weights, folded BN, optional fp32 (res) or S-layout (res_s) residual, ReLU; writes fp32 NHWC
  * y (pixel stride y_ld, channel offset y_off) and/or S-layout ys; bm/bn/nsplit force the plan
- * (0 = automatic); bm = 1000 * variant + rows also forces the main-loop variant (0 base,
- * 1 fragment prefetch, 2 prefetch with 8 waves, 4 = 128x128 with a 2-stage ring; 8 .. 11 timing
- * study: 64x64 without MFMAs / without operand loads, 128x128 8-wave prefetch the same).
+ * (0 = automatic); bm = 1000 * variant + rows also forces the kernel form on the tile (the form
+ * table of csrc/conv_forms.h: cwt_debug_conv_form says which exist; a pair it does not hold is
+ * CWT_EARG; the timing-study forms carry their own tile, which replaces the one named).
  */
 int cwt_debug_split_act(cwt_ctx* ctx, const float* x, int64_t P, int C, int ld, void* out, void* stream);
 int cwt_debug_unsplit_act(cwt_ctx* ctx, const void* s, int64_t P, int C, float* out, int ld, void* stream);
@@ -69,6 +69,15 @@ int cwt_debug_conv_x6(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int C
                       const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
                       const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
                       int nsplit, void* stream);
+
+/* The form table and the plan lookup behind these convs, on the host alone (no context, no device
+ * call).  prec: 0 conv_igemm_f32d, 1 _b16, 3 _x3s, 6 _x6.  cwt_debug_conv_form: the kernel form of
+ * variant var on tile bm x bn -> out4 = WAVES_M, WAVES_N, NSTG, PF (csrc/conv_forms.h), or
+ * CWT_EARG where the table holds no such form.  cwt_debug_conv_plan: the library's plan of the GEMM
+ * shape [M][K] x [K][Co] (batch: 0 a direct conv, else the Winograd form's GEMM count with M its
+ * tiles) -> out5 = bm, bn, var, nsplit, kt_per_split; CWT_EARG if that plan names no form. */
+int cwt_debug_conv_form(int prec, int bm, int bn, int var, int* out4);
+int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5);
 
 /* The same conv in the Winograd F(2x2, 3x3) form on the x6 arithmetic (wino.hip; the form the
  * x6 stack takes for stride-1 3x3 layers with Ci >= 256): k == 3, stride 1, pad == dil; the weights

@@ -133,6 +133,59 @@ def test_conv_s_channel_strided_out():
     assert float((yf.double() - ref).abs().max() / ref.abs().max()) < TOL
 
 
+def _small_operands(Co, seed=4):
+    N, Ci, Hi = 3, 96, 9   # CASES' (3, 96, 64, 9, 1, 1, 1, True) with Co channels out
+    x = torch.from_numpy(syn.normal(seed, "x", (N, Ci, Hi, Hi), 1.0))
+    w = torch.from_numpy(syn.normal(seed, "w", (Co, Ci, 1, 1), (2.0 / Ci) ** 0.5))
+    res = torch.from_numpy(syn.normal(seed, "r", (N, Co, Hi, Hi), 1.0))
+    return x, w, torch.ones(Co), torch.zeros(Co), res
+
+
+@pytest.mark.parametrize("var", [8, 9, 10, 11])
+def test_conv_s_timing_study_forms_launch(var):
+    """The timing-study forms (their numbers are wrong by design) launch on their own fixed tile,
+    whatever tile is named beside the variant, and the stream synchronises cleanly (run_conv_s
+    checks the return code and synchronises).  8 / 9 carry a 64x64 tile; 10 / 11 a 128x128 one, which
+    Co = 64 does not admit: there they are refused, and run on the same conv with Co = 128."""
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    L = _lib()
+    x, w, scale, shift, res = _small_operands(64)
+    if var < 10:
+        run_conv_s(x, w, scale, shift, 1, 0, 1, res, bm=1000 * var + 128, bn=64)
+        return
+    with pytest.raises(L.CwtError, match="Co % bn"):
+        run_conv_s(x, w, scale, shift, 1, 0, 1, res, bm=1000 * var + 64, bn=64)
+    x, w, scale, shift, res = _small_operands(128)
+    run_conv_s(x, w, scale, shift, 1, 0, 1, res, bm=1000 * var + 64, bn=64)
+
+
+@pytest.mark.parametrize("entry", ["cwt_debug_conv_s", "cwt_debug_conv_b16", "cwt_debug_conv_f32d", "cwt_debug_conv_x6"])
+def test_conv_form_without_a_row_is_refused(entry):
+    """A (tile, variant) the family's form table does not hold (variant 6) is CWT_EARG, an
+    argument check before any launch: the output buffer stays untouched."""
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    L = _lib()
+    dev = torch.device("cuda", 0)
+    N, Ci, Co, Hi = 1, 64, 128, 5
+    two_byte = entry in ("cwt_debug_conv_s", "cwt_debug_conv_b16")
+    xs = torch.zeros(N * Hi * Hi * Ci * 2, dtype=torch.bfloat16, device=dev)  # covers every operand layout
+    ws = torch.zeros(Co * Ci * 2, dtype=torch.bfloat16, device=dev)
+    sc, sh = torch.ones(Co, device=dev), torch.zeros(Co, device=dev)
+    y = torch.full((N, Hi, Hi, Co), float("nan"), device=dev)
+    head = (L.ctx(0), L.ptr(xs), N, Hi, Hi, Ci, L.ptr(ws), L.ptr(sc), L.ptr(sh), Co, 1, 1, 0, 1, None, Co)
+    tail = (6128, 128, 0, L.stream_ptr())
+    if two_byte:
+        rc = getattr(L.lib(), entry)(*head, None, 0, L.ptr(y), Co, 0, None, *tail)
+    else:
+        rc = getattr(L.lib(), entry)(*head, 0, L.ptr(y), Co, 0, *tail)
+    assert rc == 1001, rc
+    assert b"no such conv form" in L.lib().cwt_last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(y).all())
+
+
 def test_split_roundtrip():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
