@@ -78,7 +78,9 @@ int cwt_backbone_destroy(cwt_backbone* bb);
  * accumulation and stores the activations between convs as bf16 (the stem conv1, pooling and
  * the PPM branch stay fp32 arithmetic); the returned feature map is fp32 as before, so the
  * inner loop, the CWT and the classifier are unchanged fp32.  Applies to subsequent
- * cwt_extract_features calls with this backbone.  Returns CWT_EARG for an unknown value.
+ * cwt_extract_features calls with this backbone; cwt_extract_features_train_bn always runs
+ * the exact-fp32 convs (batch statistics amplify the bf16 rounding to O(1) feature errors).
+ * Returns CWT_EARG for an unknown value.
  */
 #define CWT_CONV_FP32 0
 #define CWT_CONV_BF16 1

@@ -158,6 +158,23 @@ int cwt_stream_destroy(void* stream);
 int cwt_debug_pretrain_op(cwt_ctx* ctx, int op, void* const* bufs, const int64_t* iargs, const float* fargs,
                           void* stream);
 
+/* Single kernels of the feature extractor's glue between the convs, on caller buffers
+ * (tests/test_gpu_backbone_ops.py).  layout: 0 fp32 NHWC, 1 the S-layout, 2 bf16 NHWC.
+ * op 0 the stem's first conv 3 -> 64, 3x3 s2 p1 (b = img [N][3][S][S] fp32, w [27][64], scale, shift,
+ * out [N*Ho*Ho][64] in layout; ia = N S layout relu), 1 max pool 3x3 s2 p1 (b = in out, NHWC in layout;
+ * ia = N H W C layout), 2 the PPM's adaptive average pooling to bins 1 2 3 6 (b = x in layout,
+ * pooled fp32 [50 * N][2048] bin-major; ia = N h w ld layout; ld is the fp32 pixel stride), 3 the
+ * PPM's grouped small-M GEMM out_g = A_g * Bt_g^T, * scale_g + shift_g and ReLU where scale_g is not
+ * NULL (b = A, Bt0..3, scale0..3, shift0..3, out; ia = M0..3, N, K, kchunk, form; A fp32 [sum M_g][K]
+ * and out [sum M_g][N] hold the groups' rows one after another, Bt_g [K][N], scale / shift all four
+ * or all NULL; form 0 the MFMA kernel, 1 the split-K kernel with K chunk kchunk (32 or 64), < 0 the
+ * extractor's own choice by sum M_g), 4 training-mode BN, in place (b = y in layout, res in the same
+ * layout or NULL, bn [4][C] = gamma beta running_mean running_var, scale [C], shift [C], the last
+ * three rewritten; ia = M C layout ld res_ld relu rows_per_image seed; fa = eps momentum drop_p;
+ * ld / res_ld the fp32 row strides), 5 bf16 -> fp32 widening (b = in out; ia = count). */
+int cwt_debug_backbone_op(cwt_ctx* ctx, int op, void* const* bufs, const int64_t* iargs, const float* fargs,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from few_shot_seg_cwt_amd import synthetic as syn  # noqa: E402
+import bf16_ref as R  # noqa: E402
 
 SEED = 2021
+TOL_B16 = 2e-5  # the bf16 conv's own bar (tests/test_gpu_conv_s.py)
+PROBES = ["layer0.1", "layer1.0.downsample.1", "layer4.2.bn3", "ppm.features.0.2", "ppm.features.3.2",
+          "bottleneck.1"]  # as tests/test_gpu_bn_train.py
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -40,24 +44,157 @@ def _transformer():
     return t
 
 
+def _images(S, n, index=11):
+    """n images [n, 3, S, S]: the supports of a synthetic (n - 1)-shot episode and its query."""
+    ep = syn.make_episode(SEED, index, S, n - 1)
+    return torch.from_numpy(np.concatenate([ep["spprt_imgs"][0], ep["qry_img"]]))
+
+
+_emul = {}
+
+
+def _emulation(layers, S, n):
+    """Once per shape, on the CPU: the images, the exact float64 (layer2, layer3, layer4, features)
+    and E_emul per layer = rel(bf16_ref.bf16_chain in fp32, exact)."""
+    from oracle import cwt_oracle as O
+    key = (layers, S, n)
+    if key not in _emul:
+        sd = O.to_torch_state(syn.make_pspnet_state(layers, SEED))
+        x = _images(S, n)
+        with torch.no_grad():
+            sd64 = R.state64(sd)
+            exact = R.exact_chain(x, sd64, layers)
+            feat = O.extract_features(x.double(), sd64, layers)
+        e_emul = [R.rel(a, b) for a, b in zip(R.bf16_chain(x, sd, layers, torch.float32), exact)]
+        _emul[key] = (x, exact, feat, e_emul)
+    return _emul[key]
+
+
 @pytest.mark.parametrize("layers,S", [(50, 129), (101, 65)])
 def test_bf16_features_close_to_fp32(dev, layers, S):
+    """The bf16 stack's features against the fp32 path's: within 2 x the error that the bf16
+    roundings themselves cost, E_emul = the CPU emulation's layer4 error against the exact
+    float64 network (bf16_ref; the rule of test_bf16_mid_features, the bar was 0.1 before).
+    Measured on the MI355X: R50@129 err 4.5e-3, E_emul 6.8e-3 (ratio 0.66), cosine 0.999997;
+    R101@65 err 5.7e-3, E_emul 1.09e-2 (ratio 0.52), cosine 0.999990."""
     sd = syn.make_pspnet_state(layers, SEED)
     m32, m16 = _models(layers, sd)
-    ep = syn.make_episode(SEED, 11, S, 2)
-    x = torch.from_numpy(np.concatenate([ep["spprt_imgs"][0], ep["qry_img"]])).to(dev)
+    x_cpu, _, _, e_emul = _emulation(layers, S, 3)
+    x = x_cpu.to(dev)
     f32, _ = m32.extract_features(x)
     f16, _ = m16.extract_features(x)
     torch.cuda.synchronize()
     assert f16.dtype == torch.float32 and f16.shape == f32.shape
     err = float((f16 - f32).abs().max() / f32.abs().max())
     cos = float(torch.nn.functional.cosine_similarity(f16.flatten(1), f32.flatten(1)).min())
-    print(f"R{layers}@{S}: bf16 vs fp32 features max rel {err:.3e}, min cosine {cos:.6f}")
-    assert err < 0.1 and cos > 0.995
+    print(f"R{layers}@{S}: bf16 vs fp32 features max rel {err:.3e}, min cosine {cos:.6f}, "
+          f"E_emul(l4) {e_emul[2]:.3e}, ratio {err / e_emul[2]:.2f}")
+    assert err <= 2 * e_emul[2] and cos > 0.995
     # switching back restores the fp32 path exactly
     m16.set_conv_dtype("fp32")
     f16b, _ = m16.extract_features(x)
     assert torch.equal(f16b, f32)
+
+
+def _mid_model(layers, **over):
+    from few_shot_seg_cwt_amd import get_model
+    m = get_model(syn.cfg_defaults(layers=layers, rmid="l34", conv_dtype="bf16", **over))
+    return m.load_state_dict(syn.make_pspnet_state(layers, SEED))
+
+
+@pytest.mark.parametrize("layers,S,n", [(50, 33, 2), (50, 65, 5)])
+def test_bf16_head_on_own_input(dev, layers, S, n):
+    """From layer4's output on nothing is rounded to bf16: on the device's own layer4 feature
+    (bf16 values, widened) the PPM + bottleneck in float64 -- the bottleneck weight bf16 over its
+    2048 layer4 channels, fp32 over its PPM channels, as load_conv / load_ppm_fold store it -- must
+    give the device's features to the bf16 conv's bar.  n = 5: 250 cells, the split-K PPM GEMMs.
+    Measured on the MI355X: rel 2.4e-7 (R50@33, N = 2) and 2.5e-7 (R50@65, N = 5)."""
+    from oracle import cwt_oracle as O
+    m = _mid_model(layers)
+    x = _images(S, n)
+    f, mids = m.extract_features(x.to(dev))
+    torch.cuda.synchronize()
+    l4 = mids[4][0].cpu()
+    assert torch.equal(l4, R.r16(l4)) and float(l4.abs().max()) > 0
+    ref = R.head(l4.double(), R.state64(O.to_torch_state(syn.make_pspnet_state(layers, SEED))), torch.float64)
+    e = R.rel(f, ref)
+    print(f"R{layers}@{S} N={n}: bf16 head on its own layer4 output, rel {e:.3e}")
+    assert e < TOL_B16
+
+
+@pytest.mark.parametrize("layers,S,n", [(50, 33, 2), (101, 33, 2)])
+def test_bf16_mid_features(dev, layers, S, n):
+    """layer2 / layer3 / layer4 outputs and the features of the bf16 stack against the exact
+    float64 oracle: E_dev <= 2 x E_emul, the error of the fp32-accumulating CPU emulation of the
+    same roundings (for the features: of its layer4).  Two emulations that differ only in their
+    accumulation precision stay within 20 % of each other; a layout bug shows at O(1).
+    Measured E_dev / E_emul on the MI355X: R50@33 l2 1.18, l3 0.94, l4 1.01, features 0.63
+    (E_emul 7.9e-3, 9.4e-3, 5.8e-3); R101@33 l2 1.18, l3 0.93, l4 0.87, features 0.56 (E_emul 7.9e-3, 1.41e-2,
+    9.2e-3).  E_emul itself moves with the host's fp32 conv (9.2e-3 for l2 on another machine)."""
+    x, exact, feat, e_emul = _emulation(layers, S, n)
+    f, mids = _mid_model(layers).extract_features(x.to(dev))
+    torch.cuda.synchronize()
+    got = {"l2": (mids[2][0], exact[0], e_emul[0]), "l3": (mids[3][0], exact[1], e_emul[1]),
+           "l4": (mids[4][0], exact[2], e_emul[2]), "features": (f, feat, e_emul[2])}
+    bad = {}
+    for k, (a, b, ee) in got.items():
+        assert tuple(a.shape) == tuple(b.shape)
+        ed = R.rel(a, b)
+        print(f"R{layers}@{S} {k}: E_dev {ed:.3e} E_emul {ee:.3e} ratio {ed / ee:.2f}")
+        if not ed <= 2 * ee:
+            bad[k] = (ed, ee)
+    assert not bad, bad
+
+
+TOL_TRAIN, TOL_TRAIN_STATS = 5e-3, 1e-3  # test_gpu_bn_train.py TOL_S33 / TOL_S33_STATS (small maps)
+
+
+def test_bf16_train_bn(dev):
+    """One training-mode extraction on a bf16 backbone, R50 at S = 65, 3 images, Dropout2d off.
+    Rounding the raw conv outputs to bf16 before their batch statistics is not usable: the CPU
+    emulation of those roundings (bf16_ref.bf16_train) is 0.59 (fp32 accumulation) / 0.56
+    (float64) off the float64 oracle's features at this shape, the two emulations 0.40 apart
+    (statistics 4e-5 .. 2e-2), far over the 5e-2 that would have made it a yardstick.  So
+    run_extract takes the exact-fp32 conv path for this pass, as for the bf16x3 arithmetic, and the
+    pass is held to the fp32 model's bars: the small-map bars of tests/test_gpu_bn_train.py (the
+    oracle itself moves 9.3e-5 between fp32 and float64 here, 1.4e-4 at their S = 33), and
+    bitwise the fp32 model's own training-mode pass.  The eval pass after it runs bf16 again.
+    Measured on the MI355X: features 1.6e-4 off the oracle, statistics 4e-8 (layer0.1) .. 9.9e-6
+    (bottleneck.1), all bitwise the fp32 model's; the eval pass after it E_dev 3.7e-3, E_emul(l4) 6.5e-3 (0.57)."""
+    from few_shot_seg_cwt_amd import get_model
+    from oracle import cwt_oracle as O
+    sd = O.to_torch_state(syn.make_pspnet_state(50, SEED))
+    x = _images(65, 3, index=7)
+    sdx = R._running_to(R.state64(sd), torch.float64)
+    f_exact = O.extract_features(x.double(), sdx, 50, train_bn_momentum=0.1)
+    e_emul = R.rel(R.bf16_train(x, sd, 50, torch.float32, 0.1)[0], f_exact)
+    print(f"bf16 train BN: the bf16 emulation's features are {e_emul:.3e} off the exact ones")
+    res = {}
+    for dt in ("bf16", "fp32"):
+        m = get_model(syn.cfg_defaults(layers=50, conv_dtype=dt, dropout=0.0))
+        m.load_state_dict(syn.make_pspnet_state(50, SEED))
+        m.train()
+        f, _ = m.extract_features(x.to(dev))
+        m.eval()
+        fe, _ = m.extract_features(x.to(dev))
+        torch.cuda.synchronize()
+        res[dt] = (f.cpu(), m.state_dict(), fe.cpu())
+    f, got, fe = res["bf16"]
+    errs = {"features": R.rel(f, f_exact)}
+    for p in PROBES:
+        for st in ("running_mean", "running_var"):
+            errs[f"{p}.{st}"] = R.rel(got[f"{p}.{st}"], sdx[f"{p}.{st}"])
+    print("bf16 train BN vs float64 oracle:", {k: f"{v:.2e}" for k, v in errs.items()})
+    assert errs.pop("features") < TOL_TRAIN
+    assert max(errs.values()) < TOL_TRAIN_STATS, errs
+    assert torch.equal(f, res["fp32"][0])
+    for k, v in res["fp32"][1].items():
+        assert torch.equal(got[k], v), k
+    # eval mode afterwards: the bf16 stack again, on the moved statistics
+    f_eval = O.extract_features(x.double(), sdx, 50)
+    e_dev, e_emul_l4 = R.rel(fe, f_eval), R.rel(R.bf16_chain(x, sdx, 50, torch.float32)[2], R.exact_chain(x, sdx, 50)[2])
+    print(f"eval after it: E_dev {e_dev:.3e} E_emul(l4) {e_emul_l4:.3e} ratio {e_dev / e_emul_l4:.2f}")
+    assert not torch.equal(fe, res["fp32"][2]) and e_dev <= 2 * e_emul_l4
 
 
 def _argmax_up(pred, S):
