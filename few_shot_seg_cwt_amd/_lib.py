@@ -311,7 +311,9 @@ def require(t: torch.Tensor, name: str, dtype=torch.float32, device=None):
 
 
 def profile_enable(level: int, device=None):
-    """0 off; 1 phases + bottleneck conv (cheap, for timed regions); 2 every launch.  Applies
+    """0 off; 1 phases + bottleneck conv (cheap, for timed regions); 2 every launch; 3 also the
+    Winograd convs' wino_in / wino_gemm / wino_out sub-records (their event pairs add ~10 us of gaps
+    inside each Winograd conv's own record, so time the convs themselves at level 1 or 2).  Applies
     to every context of the device."""
     for c in all_ctx(device):
         check(lib().cwt_profile_enable(c, int(level)), "cwt_profile_enable")

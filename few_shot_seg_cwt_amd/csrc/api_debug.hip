@@ -1,0 +1,399 @@
+// The cwt_debug_* hooks of libcwt.so (include/cwt_debug.h): single launches of the product path on
+// caller buffers, for the tests and the timing tools.
+#include <algorithm>
+#include <cstdlib>
+
+#include "../../include/cwt_debug.h"
+#include "conv_forms.h"
+#include "ctx.h"
+
+using namespace cwt;
+
+namespace cwt {
+// HW_REG_HW_ID (wave, SIMD, CU, SH, SE fields) and HW_REG_XCC_ID of each workgroup's first wave
+__global__ void census_kernel(unsigned* out) {
+  unsigned hw, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  if (threadIdx.x == 0) {
+    out[2 * blockIdx.x] = hw;
+    out[2 * blockIdx.x + 1] = xcc;
+  }
+}
+}  // namespace cwt
+
+static int debug_conv_s(cwt_ctx* ctx, int prec, const void* xs, int N, int Hi, int Wi, int Ci, const void* ws,
+                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
+                        const float* res, int res_ld, const void* res_s, int relu, float* y, int y_ld, int y_off,
+                        void* ys, int bm, int bn, int nsplit, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(xs && ws && scale && shift && (y || ys), "null buffer");
+  const int kb = prec == 1 ? 64 : 32;
+  CWT_CHECK(Ci % kb == 0 && Co % 64 == 0, prec == 1 ? "need Ci%64==0, Co%64==0" : "need Ci%32==0, Co%64==0");
+  CWT_CHECK(!y || (y_ld >= y_off + Co && y_ld % 4 == 0 && y_off % 4 == 0), "bad y stride");
+  ConvSArgs a = conv_s_geom(N, Hi, Wi, Ci, Co, k, stride, pad, dil);
+  int rc;
+  ConvPlan p = plan_conv_s(prec, a.M, a.Co, a.K);
+  if (bm > 0 && (rc = force_conv_form(prec, bm, bn, Co, &p))) return rc;  // before any device call
+  CWT_HIP(hipSetDevice(ctx->device));
+  if ((rc = zero_line(ctx, &a.zero))) return rc;
+  a.xs = (const __bf16*)xs;
+  a.ws = (const __bf16*)ws;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = res;
+  a.res_ld = res_ld;
+  a.res_s = (const __bf16*)res_s;
+  a.relu = relu;
+  a.y = y;
+  a.y_ld = y_ld;
+  a.y_off = y_off;
+  a.ys = (__bf16*)ys;
+  if (nsplit > 0) {
+    const int kt = a.K / kb;
+    p.kt_per_split = cdiv(kt, nsplit);
+    p.nsplit = cdiv(kt, p.kt_per_split);
+  }
+  if (prec == 6) {  // the fp32 packed weights -> the x6 kernel's hi | mid line and lo plane
+    __bf16 *w3s, *w3l;  // hi | mid lines (2 per weight) and the lo plane
+    if ((rc = cwt::ws(ctx, "dbg.w3s", (size_t)Co * a.K * 2, &w3s)) ||  // (cwt::ws: the parameter ws hides it)
+        (rc = cwt::ws(ctx, "dbg.w3l", (size_t)Co * a.K, &w3l)))
+      return rc;
+    // CWT_DBG_W3_CACHE=1 (timing tools that call the same conv repeatedly): split the weights only when
+    // the source buffer or its shape changes, so the timed calls are the conv alone
+    static const bool w3_cache = getenv("CWT_DBG_W3_CACHE") && getenv("CWT_DBG_W3_CACHE")[0] == '1';
+    static const void* w3_src = nullptr;
+    static long w3_n = 0;
+    static void* w3_dst = nullptr;
+    if (!(w3_cache && w3_src == ws && w3_n == (long)Co * a.K && w3_dst == w3s)) {
+      if ((rc = launch_split_w3((const float*)ws, Co, a.K, w3s, w3l, (hipStream_t)stream))) return rc;
+      w3_src = ws;
+      w3_n = (long)Co * a.K;
+      w3_dst = w3s;
+    }
+    a.ws = w3s;
+    a.ws_lo = w3l;
+  }
+  float* part = nullptr;
+  const size_t pf = (size_t)p.nsplit * a.M * a.Co;
+  if (p.nsplit > 1 && (rc = cwt::ws(ctx, "dbg.PART", pf, &part))) return rc;
+  return launch_conv_x3s(a, p, 0, part, pf, (hipStream_t)stream, prec);
+}
+
+extern "C" {
+
+int cwt_debug_conv(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, int x_ld, const float* w_packed,
+                   const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
+                   const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
+                   int nsplit, int precision, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && w_packed && scale && shift && y, "null buffer");
+  CWT_CHECK(Ci % 32 == 0 && Co % 64 == 0 && x_ld >= Ci && y_ld >= y_off + Co, "need Ci%32==0, Co%64==0");
+  CWT_HIP(hipSetDevice(ctx->device));
+  ConvLayer L;
+  L.Ci = Ci;
+  L.Co = Co;
+  L.k = k;
+  L.stride = stride;
+  L.pad = pad;
+  L.dil = dil;
+  L.w = (float*)w_packed;
+  int rc;
+  if (k > 1) {  // caller layout [Co][k][k][Ci] -> packed_k order
+    if ((rc = ws(ctx, "dbg.wpack", (size_t)Co * k * k * Ci, &L.w))) return rc;
+    if ((rc = launch_repack_cblock(w_packed, L.w, Co, k * k, Ci, (hipStream_t)stream))) return rc;
+    w_packed = L.w;
+  }
+  L.scale = (float*)scale;
+  L.shift = (float*)shift;
+  ConvCall c{0, &L, x, N, Hi, Wi, x_ld, y, y_ld, y_off, res, res_ld, relu, true};
+  ConvArgs a = make_args(c);
+  CWT_CHECK(precision == 0, "cwt_debug_conv runs the exact-fp32 conv only (bf16x3 plans: cwt_debug_conv_s)");
+  ConvPlan p = plan_conv(a.M, a.Co, a.K);
+  if (bm > 0) {
+    CWT_CHECK((bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64), "tile must be 128x128, 128x64 or 64x64");
+    CWT_CHECK(Co % bn == 0, "Co % bn");
+    p.bm = bm;
+    p.bn = bn;
+  }
+  if (nsplit > 0) {
+    const int kt = a.K / 32;
+    p.kt_per_split = cdiv(kt, nsplit);
+    p.nsplit = cdiv(kt, p.kt_per_split);
+  }
+  float* part = nullptr;
+  size_t pf = (size_t)p.nsplit * a.M * a.Co;
+  if (p.nsplit > 1 && (rc = ws(ctx, "dbg.PART", pf, &part))) return rc;
+  return launch_conv(a, p, 0, part, pf, (hipStream_t)stream);
+}
+
+int cwt_debug_census(cwt_ctx* ctx, int nblocks, unsigned* out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(out && nblocks > 0, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(census_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, out);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
+int cwt_debug_split_act(cwt_ctx* ctx, const float* x, int64_t P, int C, int ld, void* out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && out && P >= 0 && C % 32 == 0 && ld >= C && ld % 4 == 0, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_split_act(x, P, C, ld, (__bf16*)out, (hipStream_t)stream);
+}
+
+int cwt_debug_unsplit_act(cwt_ctx* ctx, const void* s, int64_t P, int C, float* out, int ld, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(s && out && P >= 0 && C % 32 == 0 && ld >= C && ld % 4 == 0, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_unsplit_act((const __bf16*)s, P, C, out, ld, (hipStream_t)stream);
+}
+
+int cwt_debug_pack_wsplit(cwt_ctx* ctx, const float* w, int Co, int k, int Ci, void* out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(w && out && Co > 0 && Ci % 32 == 0 && (k == 1 || k == 3), "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  float* wp;
+  int rc;
+  const long K = (long)k * k * Ci;
+  if ((rc = ws(ctx, "dbg.wpack", (size_t)Co * K, &wp))) return rc;
+  if ((rc = launch_repack_cblock(w, wp, Co, k * k, Ci, (hipStream_t)stream))) return rc;
+  return launch_split_act(wp, Co, (int)K, (int)K, (__bf16*)out, (hipStream_t)stream);
+}
+
+// Single kernels of run_extract's glue on caller buffers (include/cwt_debug.h has the argument
+// layouts): the launchers of the product path, their workspaces from the context.
+int cwt_debug_backbone_op(cwt_ctx* ctx, int op, void* const* b, const int64_t* ia, const float* fa, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(b && ia, "null argument");
+  CWT_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  auto lay_ok = [](int64_t l) { return l == ACT_F32 || l == ACT_SPLIT || l == ACT_BF16; };
+  float* p;
+  int rc;
+  if (op == 0) {  // stem conv1: b = img w scale shift out; ia = N S layout relu
+    const int N = (int)ia[0], S = (int)ia[1];
+    CWT_CHECK(b[0] && b[1] && b[2] && b[3] && b[4] && N > 0 && S > 0 && lay_ok(ia[2]), "stem conv1");
+    return launch_stem_conv1((const float*)b[0], N, S, (const float*)b[1], (const float*)b[2], (const float*)b[3],
+                             (float*)b[4], down2(S), st, (int)ia[2], (int)ia[3]);
+  }
+  if (op == 1) {  // max pool: b = in out; ia = N H W C layout
+    const int N = (int)ia[0], H = (int)ia[1], W = (int)ia[2], C = (int)ia[3], lay = (int)ia[4];
+    CWT_CHECK(b[0] && b[1] && N > 0 && H > 0 && W > 0 && C > 0 && lay_ok(ia[4]), "maxpool");
+    const int Ho = down2(H), Wo = down2(W);
+    if (lay == ACT_BF16) return launch_maxpool3s2_b16((const __bf16*)b[0], N, H, W, C, (__bf16*)b[1], Ho, Wo, st);
+    if (lay == ACT_SPLIT) return launch_maxpool3s2_s((const __bf16*)b[0], N, H, W, C, (__bf16*)b[1], Ho, Wo, st);
+    CWT_CHECK(C % 4 == 0, "maxpool: C % 4");
+    return launch_maxpool3s2((const float*)b[0], N, H, W, C, (float*)b[1], Ho, Wo, st);
+  }
+  if (op == 2) {  // PPM pooling: b = x pooled; ia = N h w ld layout
+    const int N = (int)ia[0], h = (int)ia[1], w = (int)ia[2], ld = (int)ia[3];
+    CWT_CHECK(b[0] && b[1] && N > 0 && h > 0 && w > 0 && ld >= 2048 && lay_ok(ia[4]), "ppm");
+    // rowseg [N][h][nseg_x <= 16][2048] + blk [N][nseg_y <= 16][nseg_x <= 16][2048]
+    if ((rc = ws(ctx, "dbg.ppm", ((size_t)N * h * 16 + (size_t)N * 256) * 2048, &p))) return rc;
+    return launch_ppm((const float*)b[0], N, h, w, ld, kBins, 4, p, (float*)b[1], st, (int)ia[4]);
+  }
+  if (op == 3) {  // PPM GEMM: b = A Bt0..3 scale0..3 shift0..3 out; ia = M0..3 N K kchunk form
+    int M[4];
+    const float *Bt[4], *sc[4], *sh[4];
+    long Mtot = 0;
+    int nbn = 0;
+    for (int q = 0; q < 4; ++q) {
+      CWT_CHECK(ia[q] > 0 && ia[q] <= 4096 && b[1 + q], "ppm gemm: problem");
+      M[q] = (int)ia[q];
+      Mtot += M[q];
+      Bt[q] = (const float*)b[1 + q];
+      sc[q] = (const float*)b[5 + q];
+      sh[q] = (const float*)b[9 + q];
+      CWT_CHECK(!sc[q] == !sh[q], "ppm gemm: scale without shift");
+      nbn += sc[q] != nullptr;
+    }
+    const int N = (int)ia[4], K = (int)ia[5], kc = (int)ia[6];
+    int form = (int)ia[7];
+    CWT_CHECK(b[0] && b[13] && N > 0 && K > 0 && (nbn == 0 || nbn == 4) && form <= 1, "ppm gemm");
+    if (form < 0) form = Mtot <= kPpmGemmMaxRows ? 0 : 1;  // run_extract's rule
+    CWT_CHECK(form == 0 || kc == 32 || kc == 64, "ppm gemm: K chunk");
+    const size_t part_floats = (size_t)(form == 0 ? 8 : K / kc) * Mtot * N;
+    if ((rc = ws(ctx, "dbg.parts", part_floats, &p))) return rc;
+    return form == 0 ? launch_ppm_gemm((const float*)b[0], K, Bt, M, 4, N, K, nbn ? sc : nullptr, nbn ? sh : nullptr,
+                                       p, part_floats, (float*)b[13], st)
+                     : launch_smallm_gemm((const float*)b[0], K, Bt, M, 4, N, K, kc, p, part_floats,
+                                          nbn ? sc : nullptr, nbn ? sh : nullptr, (float*)b[13], st);
+  }
+  if (op == 4) {  // training-mode BN: b = y res bn scale shift; ia = M C layout ld res_ld relu rows_per_image seed
+    CWT_CHECK(fa && b[0] && b[2] && b[3] && b[4] && ia[0] > 0 && ia[1] > 0 && ia[1] <= 2048 && lay_ok(ia[2]) &&
+                  ia[6] > 0,
+              "bn_train");
+    BnTrainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = b[0];
+    a.M = (long)ia[0];
+    a.C = (int)ia[1];
+    a.layout = (int)ia[2];
+    a.ld = (int)ia[3];
+    a.res = b[1];
+    a.res_ld = (int)ia[4];
+    a.relu = (int)ia[5];
+    a.rows_per_image = (long)ia[6];
+    a.seed = (unsigned long long)ia[7];
+    a.bn = (float*)b[2];
+    a.scale = (float*)b[3];
+    a.shift = (float*)b[4];
+    a.eps = fa[0];
+    a.momentum = fa[1];
+    a.drop_p = fa[2];
+    CWT_CHECK(a.layout != ACT_F32 || a.ld >= a.C, "bn_train: ld < C");
+    const size_t pf = bn_train_part_floats(a.M, a.C);
+    float* bsc;
+    if ((rc = ws(ctx, "dbg.bn.part", pf, &p)) || (rc = ws(ctx, "dbg.bn.bsc", 2 * 2048, &bsc))) return rc;
+    return launch_bn_train(a, p, pf, bsc, st);
+  }
+  if (op == 5) {  // widen: b = in out; ia = count
+    CWT_CHECK(b[0] && b[1] && ia[0] > 0, "widen");
+    return launch_widen_bf16((const __bf16*)b[0], (long)ia[0], (float*)b[1], st);
+  }
+  return fail(CWT_EARG, "cwt_debug_backbone_op: unknown op");
+}
+
+int cwt_debug_conv_s(cwt_ctx* ctx, const void* xs, int N, int Hi, int Wi, int Ci, const void* ws, const float* scale,
+                     const float* shift, int Co, int k, int stride, int pad, int dil, const float* res, int res_ld,
+                     const void* res_s, int relu, float* y, int y_ld, int y_off, void* ys, int bm, int bn, int nsplit,
+                     void* stream) {
+  return debug_conv_s(ctx, 3, xs, N, Hi, Wi, Ci, ws, scale, shift, Co, k, stride, pad, dil, res, res_ld, res_s, relu, y,
+                      y_ld, y_off, ys, bm, bn, nsplit, stream);
+}
+
+int cwt_debug_conv_f32d(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
+                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
+                        const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
+                        int nsplit, void* stream) {
+  return debug_conv_s(ctx, 0, x, N, Hi, Wi, Ci, w_packed, scale, shift, Co, k, stride, pad, dil, res, res_ld, nullptr,
+                      relu, y, y_ld, y_off, nullptr, bm, bn, nsplit, stream);
+}
+
+int cwt_debug_conv_x6(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
+                      const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
+                      const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
+                      int nsplit, void* stream) {
+  return debug_conv_s(ctx, 6, x, N, Hi, Wi, Ci, w_packed, scale, shift, Co, k, stride, pad, dil, res, res_ld, nullptr,
+                      relu, y, y_ld, y_off, nullptr, bm, bn, nsplit, stream);
+}
+
+int cwt_debug_conv_form(int prec, int bm, int bn, int var, int* out4) {
+  CWT_CHECK(out4, "out4 is NULL");
+  const ConvForm* f = find_conv_form(prec, bm, bn, var);
+  if (!f) return fail(CWT_EARG, "no such conv form (conv_forms.h)");
+  out4[0] = f->waves_m;
+  out4[1] = f->waves_n;
+  out4[2] = f->nstg;
+  out4[3] = f->pf;
+  return 0;
+}
+
+int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5) {
+  CWT_CHECK(out5 && M > 0 && Co > 0 && K > 0 && batch >= 0, "bad arguments");
+  CWT_CHECK(prec == 0 || prec == 1 || prec == 3 || prec == 6, "prec must be 0, 1, 3 or 6");
+  const ConvPlan p = plan_conv_s(prec, M, Co, K, batch);
+  const int v[5] = {p.bm, p.bn, p.var, p.nsplit, p.kt_per_split};
+  std::copy(v, v + 5, out5);
+  if (!find_conv_form(prec, p.bm, p.bn, p.var)) return fail(CWT_EARG, "the plan's form is no such conv form");
+  return 0;
+}
+
+int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
+                       const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
+                       const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
+                       int nsplit, void* stream) {
+  const int m = nsplit == 4 ? 4 : 2;  // nsplit selects the output tile: 4 = F(4x4,3x3), else F(2x2,3x3)
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && w_packed && scale && shift && y, "null buffer");
+  CWT_CHECK(nsplit == 0 || nsplit == 1 || nsplit == 2 || nsplit == 4, "nsplit (the Winograd tile) must be 0, 2 or 4");
+  CWT_CHECK(k == 3 && stride == 1 && pad == dil && dil >= 1, "winograd form: 3x3, stride 1, padding = dilation");
+  CWT_CHECK(Ci % 32 == 0 && Co % 64 == 0 && N >= 1 && Hi >= 1 && Wi >= 1, "need Ci % 32 == 0, Co % 64 == 0");
+  CWT_CHECK(y_ld >= y_off + Co && y_ld % 4 == 0 && y_off % 4 == 0 && (!res || res_ld % 4 == 0), "bad strides");
+  int rc;
+  ConvPlan named;  // refused here, before the weights' transform is launched (run_wino_conv forces it)
+  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &named))) return rc;
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  const int P = (m + 2) * (m + 2);
+  const size_t n = (size_t)P * Co * Ci;
+  float* U;
+  __bf16 *us, *ul;  // split like ConvLayer's wino_s / wino_l
+  if ((rc = ws(ctx, "dbg.wU", n, &U)) || (rc = ws(ctx, "dbg.wUs", n * 2, &us)) || (rc = ws(ctx, "dbg.wUl", n, &ul)))
+    return rc;
+  // CWT_DBG_W3_CACHE=1: transform and split the weights only when their source or shape changes
+  static const bool w3_cache = getenv("CWT_DBG_W3_CACHE") && getenv("CWT_DBG_W3_CACHE")[0] == '1';
+  static const void* u_src = nullptr;
+  static long u_n = 0;
+  static void* u_dst = nullptr;
+  if (!(w3_cache && u_src == w_packed && u_n == (long)n * m && u_dst == us)) {
+    if ((rc = launch_wino_weights(w_packed, Co, Ci, U, st, m)) ||
+        (rc = launch_split_w3(U, (long)P * Co, Ci, us, ul, st)))
+      return rc;
+    u_src = w_packed;
+    u_n = (long)n * m;
+    u_dst = us;
+  }
+  return run_wino_conv(ctx, x, N, Hi, Wi, Ci, Co, dil, m, us, ul, scale, shift, res, res_ld, relu, y, y_ld, y_off, 0,
+                       st, bm, bn);
+}
+
+int cwt_debug_conv_b16(cwt_ctx* ctx, const void* xs, int N, int Hi, int Wi, int Ci, const void* ws, const float* scale,
+                       const float* shift, int Co, int k, int stride, int pad, int dil, const float* res, int res_ld,
+                       const void* res_s, int relu, float* y, int y_ld, int y_off, void* ys, int bm, int bn,
+                       int nsplit, void* stream) {
+  return debug_conv_s(ctx, 1, xs, N, Hi, Wi, Ci, ws, scale, shift, Co, k, stride, pad, dil, res, res_ld, res_s, relu, y,
+                      y_ld, y_off, ys, bm, bn, nsplit, stream);
+}
+
+// one CenterPivotConv4d layer (+ ReLU) on [B][NA][NB][cin] -> [B][NA][NB][cout] (launch_cp4d_layer);
+// variant 0 the automatic kernel choice, 1 never the rolling-window form, 2 only it
+int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
+                         const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
+                         void* stream) {
+  if (!ctx || !x || !Wa || !ba || !Wb || !bb || !y) return fail(CWT_EARG, "null argument");
+  if (B < 1 || hA < 1 || wA < 1 || hB < 1 || wB < 1) return fail(CWT_EARG, "bad shape");
+  return launch_cp4d_layer_variant(x, B, hA, wA, hB, wB, cin, cout, Wa, ba, Wb, bb, y, variant, (hipStream_t)stream);
+}
+
+int cwt_debug_occupy(cwt_ctx* ctx, int nwg, int us, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(nwg >= 1 && nwg <= 256 && us >= 1 && us <= 100000, "occupy: 1 <= nwg <= 256, 1 <= us <= 100000");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_occupy(nwg, us, (hipStream_t)stream);
+}
+
+int cwt_debug_tail_stamps(cwt_ctx* ctx, unsigned long long* host_out, int64_t max_count, int64_t* count) {
+  if (!ctx || !count) return fail(CWT_EARG, "null argument");
+  CWT_HIP(hipSetDevice(ctx->device));
+  auto it = ctx->ws.find("tail.stamps");
+  *count = (it == ctx->ws.end() || !ctx->tail_stamp_G) ? 0 : (int64_t)ctx->tail_stamp_G * 16;
+  if (host_out && *count > 0 && max_count > 0) {
+    CWT_HIP(hipDeviceSynchronize());
+    CWT_HIP(hipMemcpy(host_out, it->second.p, (size_t)std::min<int64_t>(max_count, *count) * 8, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int cwt_debug_adapt_stamps(cwt_ctx* ctx, unsigned long long* host_out, int64_t max_count, int64_t* count) {
+  if (!ctx || !count) return fail(CWT_EARG, "null argument");
+  CWT_HIP(hipSetDevice(ctx->device));
+  *count = g_adapt_stamps ? g_adapt_stamps_n : 0;
+  if (host_out && g_adapt_stamps && max_count > 0) {
+    CWT_HIP(hipDeviceSynchronize());
+    CWT_HIP(hipMemcpy(host_out, g_adapt_stamps, (size_t)std::min<int64_t>(max_count, g_adapt_stamps_n) * 8,
+                      hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int cwt_debug_adapt_spin_limit(cwt_ctx* ctx, int64_t limit) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(limit >= 0, "limit must be >= 0");
+  ctx->adapt_spin_limit = (long)limit;
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,453 @@
+// Episode entry points of libcwt.so (include/cwt.h): the inner adaptation loop and its fused tail,
+// the CWT attention forward / backward / inference, the classifiers, metrics, losses and the SGD step.
+#include <algorithm>
+#include <cstdlib>
+
+#include "ctx.h"
+#include "tail_body.h"
+
+using namespace cwt;
+
+extern "C" {
+
+int cwt_inner_adapt_batch(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int E, int n, int h, int w, int C,
+                          int S, float lr, int iters, float* W_inout, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(f_s && s_label && W_inout, "null buffer");
+  CWT_CHECK(C == 512, "C must be 512");
+  CWT_CHECK(E >= 1 && E <= 64 && n >= 1 && h >= 2 && w >= 2 && iters >= 0, "bad sizes");
+  CWT_CHECK(S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1), "need S-1 == 8*(h-1) == 8*(w-1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void *fws, *lbl, *sc, *acc, *wb, *dargs;
+  size_t b_f, b_lbl, b_sc, b_acc, b_wb, b_args;
+  adapt_ws_sizes(E, n, h, w, S, &b_f, &b_lbl, &b_sc, &b_acc, &b_wb, &b_args);
+  int rc;
+  if ((rc = ensure_ws(ctx, "adapt.f", b_f, &fws)) || (rc = ensure_ws(ctx, "adapt.args", b_args, &dargs)) ||
+      (rc = ensure_ws(ctx, "adapt.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "adapt.sc", b_sc, &sc)) ||
+      (rc = ensure_ws(ctx, "adapt.acc", b_acc, &acc)) ||  // [E][3][ADAPT_RMAX][512]
+      (rc = ensure_ws(ctx, "adapt.wbuf", b_wb, &wb)))
+    return rc;
+  // algorithmic work: per step 2 x (2*2*C*h*w*n) FLOPs; minimal bytes = f_s + labels once per step
+  Prof p(ctx, (hipStream_t)stream,
+         "inner_adapt x" + std::to_string(iters) + (E > 1 ? " E=" + std::to_string(E) : "") + " [" +
+             adapt_kernel_name(E, n, h, w, iters, ctx->adapt_upw) + "]",
+         (double)E * iters * 2.0 * (4.0 * C * h * w * n), (double)E * iters * ((double)n * h * w * C * 4 + (double)n * S * S),
+         1);
+  // the persistent kernel alone (no label prep / setup kernels): the launch rocprofv3 times
+  const char* kname = adapt_kernel_name(E, n, h, w, iters, ctx->adapt_upw);
+  const bool persist_k = strncmp(kname, "adapt_persist", 13) == 0;
+  Prof pk(ctx, (hipStream_t)stream, std::string("inner_adapt_kernel [") + kname + "]",
+          (double)E * iters * 2.0 * (4.0 * C * h * w * n), (double)E * iters * ((double)n * h * w * C * 4 + (double)n * S * S),
+          1, persist_k);
+  rc = launch_adapt(f_s, s_label, E, n, h, w, S, lr, iters, W_inout, (float*)fws, (uint8_t*)lbl, (AdaptScalars*)sc,
+                    (float*)acc, (float*)wb, (AdaptDevArgs*)dargs, ctx->use_graph ? &ctx->adapt_graphs : nullptr,
+                    ctx->adapt_upw, ctx->status_dev, ctx->adapt_spin_limit, (hipStream_t)stream, pk.ev0(), pk.ev1());
+  p.end();
+  return rc;
+}
+
+int cwt_inner_adapt(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w, int C, int S,
+                    float lr, int iters, float* W_inout, void* stream) {
+  return cwt_inner_adapt_batch(ctx, f_s, s_label, 1, n, h, w, C, S, lr, iters, W_inout, stream);
+}
+
+int cwt_normalize(cwt_ctx* ctx, const float* f, int B, int P_per_b, int C, float* out, const float* W0,
+                  float* logits0, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(f && out && C == 512 && B >= 1 && P_per_b >= 1, "bad arguments");
+  CWT_CHECK((W0 == nullptr) == (logits0 == nullptr), "W0 and logits0 go together");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_normalize(f, B, P_per_b, out, W0, logits0, (hipStream_t)stream);
+}
+
+size_t cwt_attention_saved_floats(int B, int hw, int C, int H) { return attention_saved_floats(B, hw, C, H); }
+
+int cwt_attention_fwd_train(cwt_ctx* ctx, const float* q, const float* f, int B, int hw, int C, int H,
+                            const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w,
+                            const float* ln_b, float* out, float* saved, float attn_dropout, float out_dropout,
+                            uint64_t seed, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(q && f && w_qkvs && fc_w && fc_b && ln_w && ln_b && out, "null buffer");
+  CWT_CHECK(B >= 1 && B <= 4 && hw >= 1 && C == 512, "need 1 <= B <= 4, C == 512");
+  CWT_CHECK(attn_dropout >= 0.f && attn_dropout < 1.f && out_dropout >= 0.f && out_dropout < 1.f,
+            "dropout probabilities must lie in [0, 1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  float* buf;
+  int rc;
+  if ((rc = ws(ctx, "attn.ws", attention_ws_floats(B, hw, C, H), &buf))) return rc;
+  // reference-formulation FLOPs: k/v projections 2 x 2*hw*C*C*H + QK^T/AV 2 x 2*H*2*hw*C
+  Prof p(ctx, (hipStream_t)stream, "attention_fwd",
+         (double)B * (2.0 * 2.0 * hw * C * C * H + 2.0 * 2.0 * H * 2.0 * hw * C),
+         4.0 * ((double)B * hw * C + 2.0 * H * C * C + 2.0 * C), 1);
+  rc = attention_fwd(q, f, B, hw, C, H, w_qkvs, fc_w, fc_b, ln_w, ln_b, out, saved, buf, (hipStream_t)stream,
+                     attn_dropout, out_dropout, (unsigned long long)seed);
+  p.end();
+  return rc;
+}
+
+int cwt_attention_fwd(cwt_ctx* ctx, const float* q, const float* f, int B, int hw, int C, int H,
+                      const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w, const float* ln_b,
+                      float* out, float* saved, void* stream) {
+  return cwt_attention_fwd_train(ctx, q, f, B, hw, C, H, w_qkvs, fc_w, fc_b, ln_w, ln_b, out, saved, 0.f, 0.f, 0,
+                                 stream);
+}
+
+int cwt_attention_bwd_train(cwt_ctx* ctx, const float* q, const float* f, int B, int hw, int C, int H,
+                            const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w,
+                            const float* ln_b, const float* saved, const float* d_out, float* g_w_qkvs, float* g_fc_w,
+                            float* g_fc_b, float* g_ln_w, float* g_ln_b, float attn_dropout, float out_dropout,
+                            uint64_t seed, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(q && f && w_qkvs && fc_w && fc_b && ln_w && ln_b && saved && d_out, "null buffer");
+  CWT_CHECK(g_w_qkvs && g_fc_w && g_fc_b && g_ln_w && g_ln_b, "null gradient buffer");
+  CWT_CHECK(B >= 1 && B <= 4 && hw >= 1 && C == 512, "need 1 <= B <= 4, C == 512");
+  CWT_CHECK(attn_dropout >= 0.f && attn_dropout < 1.f && out_dropout >= 0.f && out_dropout < 1.f,
+            "dropout probabilities must lie in [0, 1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  float* buf;
+  int rc;
+  if ((rc = ws(ctx, "attn.bws", attention_bwd_ws_floats(B, hw, C, H), &buf))) return rc;
+  return attention_bwd(q, f, B, hw, C, H, w_qkvs, fc_w, fc_b, ln_w, ln_b, saved, d_out, g_w_qkvs, g_fc_w, g_fc_b,
+                       g_ln_w, g_ln_b, buf, (hipStream_t)stream, attn_dropout, out_dropout, (unsigned long long)seed);
+}
+
+int cwt_attention_bwd(cwt_ctx* ctx, const float* q, const float* f, int B, int hw, int C, int H,
+                      const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w, const float* ln_b,
+                      const float* saved, const float* d_out, float* g_w_qkvs, float* g_fc_w, float* g_fc_b,
+                      float* g_ln_w, float* g_ln_b, void* stream) {
+  return cwt_attention_bwd_train(ctx, q, f, B, hw, C, H, w_qkvs, fc_w, fc_b, ln_w, ln_b, saved, d_out, g_w_qkvs,
+                                 g_fc_w, g_fc_b, g_ln_w, g_ln_b, 0.f, 0.f, 0, stream);
+}
+
+int cwt_attention_infer(cwt_ctx* ctx, const float* q, const float* f, int B, int hw, int C, int H,
+                        const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w,
+                        const float* ln_b, int64_t params_version, float* out, float* inv_norm, float* logits0,
+                        void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(q && f && w_qkvs && fc_w && fc_b && ln_w && ln_b && out && inv_norm, "null buffer");
+  CWT_CHECK(B >= 1 && B <= 4 && hw >= 1 && hw <= 512 * 32 && C == 512 && H == 4,
+            "need 1 <= B <= 4, 1 <= hw <= 16384, C == 512, H == 4");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  float *fold, *buf;
+  int rc;
+  if ((rc = ws(ctx, "attn.fold", attention_fold_floats(C, H), &fold)) ||
+      (rc = ws(ctx, "attn.iws", std::max(attention_infer_ws_floats(B, hw, C, H), (size_t)4 << 20), &buf)))
+    return rc;
+  Prof p(ctx, st, "attention_fwd", (double)B * (2.0 * 2.0 * hw * C * C * H + 2.0 * 2.0 * H * 2.0 * hw * C),
+         4.0 * ((double)B * hw * C + 2.0 * H * C * C + 2.0 * C), 1);
+  if (ctx->fold_w != w_qkvs || ctx->fold_fc != fc_w || ctx->fold_ver != params_version || ctx->fold_H != H) {
+    if ((rc = attention_fold(w_qkvs, fc_w, C, H, fold, buf, (size_t)4 << 20, st))) return rc;
+    ctx->fold_w = w_qkvs;
+    ctx->fold_fc = fc_w;
+    ctx->fold_ver = params_version;
+    ctx->fold_H = H;
+  }
+  rc = attention_infer(q, f, B, hw, C, H, fold, fc_b, ln_w, ln_b, out, inv_norm, logits0, buf, st);
+  p.end();
+  return rc;
+}
+
+int cwt_episode_tail(cwt_ctx* ctx, const float* q, const float* f, int B, int h, int w, int S, const int64_t* q_label,
+                     const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w, const float* ln_b,
+                     int64_t params_version, float* out, float* logits, float* logits0, float* iut, double* ce,
+                     float* iut0, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(q && f && q_label && w_qkvs && fc_w && fc_b && ln_w && ln_b && out && logits && logits0 && iut && ce && iut0,
+            "null buffer");
+  const int hw = h * w;
+  CWT_CHECK(B >= 1 && B <= 4 && h >= 1 && w >= 1 && hw <= 512 * 32 && S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1),
+            "need 1 <= B <= 4, h*w <= 16384, S - 1 == 8 (h - 1) == 8 (w - 1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  constexpr int C = 512, H = 4;
+  int cu = 0;
+  CWT_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  // G co-resident 512-thread workgroups (~54 KB of LDS each): the whole chip (up to 256)
+  // on a context that runs alone; 64 on one whose inner loop shares the chip with another
+  // stream's extractor pass (cwt_ctx_set_adapt_units >= 2: EpisodePipeline's adapt context).
+  // CWT_TAIL_G for A/B
+  int G = std::min(ctx->adapt_upw >= 2 ? 64 : 256, cu);
+  if (const char* gs = getenv("CWT_TAIL_G")) G = std::max(1, std::min(atoi(gs), cu));
+  float *fold, *buf;
+  unsigned* cnt;
+  int rc;
+  if ((rc = ws(ctx, "attn.fold", attention_fold_floats(C, H), &fold)) ||
+      (rc = ws(ctx, "tail.ws", std::max(episode_tail_ws_floats(B, hw, G), (size_t)4 << 20), &buf)) ||
+      (rc = ws(ctx, "tail.cnt", episode_tail_cnt_words(), &cnt)))
+    return rc;
+  // phase record (the fold when the parameters changed + the launch) and the kernel alone
+  Prof p(ctx, st, "post_loop_tail", (double)B * (2.0 * 2.0 * hw * C * C * H + 2.0 * 2.0 * H * 2.0 * hw * C),
+         4.0 * ((double)B * hw * C + 2.0 * H * C * C + 2.0 * C), 1);
+  Prof pk(ctx, st, "episode_tail_kernel", (double)B * (2.0 * 2.0 * hw * C * C * H + 2.0 * 2.0 * H * 2.0 * hw * C),
+          4.0 * ((double)B * hw * C * 2 + 2.0 * H * C * C) + 9.0 * B * S * S, 1, true);
+  if (ctx->fold_w != w_qkvs || ctx->fold_fc != fc_w || ctx->fold_ver != params_version || ctx->fold_H != H) {
+    if ((rc = attention_fold(w_qkvs, fc_w, C, H, fold, buf, (size_t)4 << 20, st))) return rc;
+    ctx->fold_w = w_qkvs;
+    ctx->fold_fc = fc_w;
+    ctx->fold_ver = params_version;
+    ctx->fold_H = H;
+  }
+  if (ctx->tail_epoch > episode_tail_max_epoch(G) || ctx->tail_G != G) {  // fresh, wrapped, aborted or re-sized
+    CWT_HIP(hipMemsetAsync(cnt, 0, episode_tail_cnt_words() * 4, st));
+    ctx->tail_epoch = 0;
+    ctx->tail_G = G;
+  }
+  // timing study (CWT_TAIL_STAMPS=1): per-workgroup phase stamps (cwt_debug_tail_stamps)
+  unsigned long long* stamps = nullptr;
+  if (getenv("CWT_TAIL_STAMPS") && getenv("CWT_TAIL_STAMPS")[0] == '1' &&
+      (rc = ws(ctx, "tail.stamps", (size_t)G * 16, &stamps)))
+    return rc;
+  ctx->tail_stamp_G = stamps ? G : 0;
+  if (pk.ev0()) CWT_HIP(hipEventRecord(pk.ev0(), st));
+  rc = launch_episode_tail(q, f, B, hw, h, w, S, q_label, fold, fc_b, ln_w, ln_b, out, logits, logits0, iut, ce, iut0,
+                           buf, cnt, ctx->tail_epoch++, G, ctx->adapt_spin_limit,
+                           ctx->status_dev + 1, st, stamps);  // the tail's status word
+  if (pk.ev1()) CWT_HIP(hipEventRecord(pk.ev1(), st));
+  p.end();
+  return rc;
+}
+
+// cwt_inner_adapt_tail fuses the tail into the loop's launch where the loop runs as the two-unit
+// register form (EpisodePipeline's adapt context) in its product instantiation
+static bool fused_tail_applies(cwt_ctx* ctx, int n, int h, int w, int iters) {
+  const char* kname = adapt_kernel_name(1, n, h, w, iters, ctx->adapt_upw);
+  const char* dbg = getenv("CWT_ADAPT_DBG");
+  const char* fz = getenv("CWT_FUSED_LOOP_TAIL");
+  const char* tst = getenv("CWT_TAIL_STAMPS");
+  return strcmp(kname, "adapt_persist_kernel<5") == 0 && !(dbg && atoi(dbg) != 0) && !(fz && fz[0] == '0') &&
+         !(tst && tst[0] == '1');
+}
+
+int cwt_inner_adapt_tail(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w, int C, int S,
+                         float lr, int iters, float* W_inout, const float* f_q, const int64_t* q_label,
+                         const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w,
+                         const float* ln_b, int64_t params_version, float* out, float* logits, float* logits0,
+                         float* iut, double* ce, float* iut0, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(f_s && s_label && W_inout && f_q && q_label && w_qkvs && fc_w && fc_b && ln_w && ln_b && out && logits &&
+                logits0 && iut && ce && iut0,
+            "null buffer");
+  CWT_CHECK(C == 512, "C must be 512");
+  CWT_CHECK(n >= 1 && h >= 2 && w >= 2 && iters >= 0 && h * w <= 512 * 32, "bad sizes");
+  CWT_CHECK(S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1), "need S-1 == 8*(h-1) == 8*(w-1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  // fused where the loop runs as the two-unit register form (EpisodePipeline's adapt context) in
+  // its product instantiation; everything else (and CWT_FUSED_LOOP_TAIL=0) runs the two calls
+  if (!fused_tail_applies(ctx, n, h, w, iters)) {
+    int rc = cwt_inner_adapt(ctx, f_s, s_label, n, h, w, C, S, lr, iters, W_inout, stream);
+    if (rc) return rc;
+    return cwt_episode_tail(ctx, W_inout, f_q, 1, h, w, S, q_label, w_qkvs, fc_w, fc_b, ln_w, ln_b, params_version, out,
+                            logits, logits0, iut, ce, iut0, stream);
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  constexpr int H = 4;
+  const int hw = h * w;
+  const int G = adapt_persist_workgroups(1, n, h, w, iters, ctx->adapt_upw);
+  CWT_CHECK(G >= 1 && G <= 512, "fused tail: loop geometry");
+  // the loop's workspaces (cwt_inner_adapt_batch)
+  void *fws, *lbl, *sc, *acc, *wb, *dargs;
+  size_t b_f, b_lbl, b_sc, b_acc, b_wb, b_args;
+  adapt_ws_sizes(1, n, h, w, S, &b_f, &b_lbl, &b_sc, &b_acc, &b_wb, &b_args);
+  int rc;
+  if ((rc = ensure_ws(ctx, "adapt.f", b_f, &fws)) || (rc = ensure_ws(ctx, "adapt.args", b_args, &dargs)) ||
+      (rc = ensure_ws(ctx, "adapt.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "adapt.sc", b_sc, &sc)) ||
+      (rc = ensure_ws(ctx, "adapt.acc", b_acc, &acc)) || (rc = ensure_ws(ctx, "adapt.wbuf", b_wb, &wb)))
+    return rc;
+  // the tail's (cwt_episode_tail), over the loop's G workgroups
+  float *fold, *tws, *wq;
+  unsigned* cnt;
+  if ((rc = ws(ctx, "attn.fold", attention_fold_floats(C, H), &fold)) ||
+      (rc = ws(ctx, "tail.ws", std::max(episode_tail_ws_floats(1, hw, G), (size_t)4 << 20), &tws)) ||
+      (rc = ws(ctx, "tail.cnt", episode_tail_cnt_words(), &cnt)) || (rc = ws(ctx, "tail.wq", (size_t)G * 2 * C, &wq)))
+    return rc;
+  if (ctx->fold_w != w_qkvs || ctx->fold_fc != fc_w || ctx->fold_ver != params_version || ctx->fold_H != H) {
+    if ((rc = attention_fold(w_qkvs, fc_w, C, H, fold, tws, (size_t)4 << 20, st))) return rc;
+    ctx->fold_w = w_qkvs;
+    ctx->fold_fc = fc_w;
+    ctx->fold_ver = params_version;
+    ctx->fold_H = H;
+  }
+  if (ctx->tail_epoch > episode_tail_max_epoch(G) || ctx->tail_G != G) {  // fresh, wrapped, aborted or re-sized
+    CWT_HIP(hipMemsetAsync(cnt, 0, episode_tail_cnt_words() * 4, st));
+    ctx->tail_epoch = 0;
+    ctx->tail_G = G;
+  }
+  // this launch's stamp slot: {start (min), loop end (max), tail end (max)}, pre-set {~0, 0, 0}; only
+  // when the profile records it (otherwise no memsets on the adapt stream and no stamp atomics: the
+  // kernel guards every use of a null slot)
+  constexpr int kFSlots = 4096;
+  int slot = -1;
+  unsigned long long* fst = nullptr;
+  if (ctx->prof_level >= 1) {
+    if (!ctx->fstamps) CWT_HIP(hipMalloc(&ctx->fstamps, (size_t)kFSlots * 3 * sizeof(unsigned long long)));
+    slot = ctx->fstamp_next;
+    ctx->fstamp_next = (ctx->fstamp_next + 1) % kFSlots;
+    fst = ctx->fstamps + 3 * slot;
+    CWT_HIP(hipMemsetAsync(fst, 0xFF, sizeof(unsigned long long), st));
+    CWT_HIP(hipMemsetAsync(fst + 1, 0, 2 * sizeof(unsigned long long), st));
+  }
+  TailArgs ta;
+  if ((rc = fill_episode_tail_args(W_inout, f_q, 1, hw, h, w, S, q_label, fold, fc_b, ln_w, ln_b, out, logits, logits0,
+                                   iut, ce, iut0, tws, cnt, ctx->tail_epoch++, G, ctx->adapt_spin_limit,
+                                   ctx->status_dev + 1, nullptr, &ta)))
+    return rc;
+  const FusedTail ft{&ta, wq, fst};
+  const std::string kn = "adapt_persist_tail_kernel<5";
+  const double lfl = (double)iters * 2.0 * (4.0 * C * h * w * n), lby = (double)iters * ((double)n * h * w * C * 4 + (double)n * S * S);
+  const double tfl = 2.0 * 2.0 * hw * C * C * H + 2.0 * 2.0 * H * 2.0 * hw * C;
+  Prof p(ctx, st, "inner_adapt x" + std::to_string(iters) + " [" + kn + "]", lfl, lby, 1);
+  // the launch's loop part and tail part (its stamps; the events only order the read-back)
+  Prof pk(ctx, st, "inner_adapt_kernel [" + kn + "]", lfl, lby, 1, true);
+  if (pk.idx >= 0) ctx->recs[pk.idx].fslot = slot;
+  rc = launch_adapt(f_s, s_label, 1, n, h, w, S, lr, iters, W_inout, (float*)fws, (uint8_t*)lbl, (AdaptScalars*)sc,
+                    (float*)acc, (float*)wb, (AdaptDevArgs*)dargs, nullptr, ctx->adapt_upw, ctx->status_dev,
+                    ctx->adapt_spin_limit, st, pk.ev0(), pk.ev1(), &ft);
+  p.end();
+  if (rc) return rc;
+  for (const char* tn : {"post_loop_tail", "episode_tail_kernel"}) {
+    Prof pt(ctx, st, tn, tfl, 4.0 * ((double)hw * C * 2 + 2.0 * H * C * C) + 9.0 * S * S, 1);
+    pt.end();
+    if (pt.idx >= 0) {
+      ctx->recs[pt.idx].fslot = slot;
+      ctx->recs[pt.idx].fpart = 1;
+    }
+  }
+  return 0;
+}
+
+int cwt_classify_scaled(cwt_ctx* ctx, const float* W, const float* f, const float* inv_norm, int B, int P, int C,
+                        float* logits, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(W && f && inv_norm && logits && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_classify_scaled(W, f, inv_norm, B, P, logits, (hipStream_t)stream);
+}
+
+int cwt_classify(cwt_ctx* ctx, const float* W, const float* f, int B, int P, int C, float* logits, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(W && f && logits && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_classify(W, f, B, P, logits, (hipStream_t)stream);
+}
+
+int cwt_classify_bwd(cwt_ctx* ctx, const float* dlogits, const float* f, int B, int P, int C, float* dW,
+                     void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(dlogits && f && dW && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_classify_bwd(dlogits, f, B, P, dW, (hipStream_t)stream);
+}
+
+int cwt_cos_classify(cwt_ctx* ctx, const float* x, int B, int P, int C, int n, float* weight, const float* g,
+                     const float* bias, const float* scale, int mode, float* out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && weight && scale && out && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_CHECK(n >= 1 && n <= 64, "n_classes must be in [1, 64]");
+  CWT_CHECK(mode >= 0 && mode <= 3 && (!(mode & 1) || g), "mode: bit 0 WeightNorm (needs g), bit 1 weight_norm");
+  CWT_HIP(hipSetDevice(ctx->device));
+  float *weff, *vn;
+  int rc;
+  if ((rc = ws(ctx, "heads.weff", (size_t)n * C, &weff)) || (rc = ws(ctx, "heads.vnorm", 64, &vn))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = launch_cos_weight(weight, g, n, C, mode, weff, vn, st))) return rc;
+  return launch_cos_cls_fwd(x, P, B, n, weff, bias, scale, out, st);
+}
+
+int cwt_cos_classify_bwd(cwt_ctx* ctx, const float* x, int B, int P, int C, int n, float* weight, const float* g,
+                         const float* bias, const float* scale, int mode, const float* dscores, float* d_weight,
+                         float* d_g, float* d_bias, float* d_scale, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && weight && scale && dscores && d_weight && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_CHECK(n >= 1 && n <= 64, "n_classes must be in [1, 64]");
+  CWT_CHECK(mode >= 0 && mode <= 3 && (!(mode & 1) || (g && d_g)), "mode: bit 0 WeightNorm (needs g, d_g)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const int nb = cos_cls_bwd_blocks((long)B * P);
+  float *weff, *vn, *part, *parts;
+  int rc;
+  if ((rc = ws(ctx, "heads.weff", (size_t)n * C, &weff)) || (rc = ws(ctx, "heads.vnorm", 64, &vn)) ||
+      (rc = ws(ctx, "heads.part", (size_t)nb * n * C, &part)) ||
+      (rc = ws(ctx, "heads.parts", (size_t)nb * n * 2, &parts)))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the forward's weight (for weight_norm the stored weight is already normalised: idempotent)
+  if ((rc = launch_cos_weight(weight, g, n, C, mode, weff, vn, st))) return rc;
+  return launch_cos_cls_bwd(x, P, B, n, weff, bias, scale, dscores, part, parts, mode, weight, g, vn, d_weight, d_g,
+                            d_bias, d_scale, st);
+}
+
+int cwt_seg_metrics(cwt_ctx* ctx, const float* logits, const int64_t* target, int B, int h, int w, int S,
+                    float* iut_out, double* ce_out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits && target && iut_out && B >= 1 && B <= 64 && h >= 1 && w >= 1 && S >= 1, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void* cnt;
+  int rc;
+  if ((rc = ensure_ws(ctx, "metrics.cnt", (size_t)B * 256 * (2 * 6 * 4 + 2 * 8) + 16, &cnt))) return rc;
+  return launch_seg_metrics(logits, target, B, h, w, S, iut_out, ce_out, (unsigned*)cnt, (hipStream_t)stream);
+}
+
+int cwt_seg_metrics_pair(cwt_ctx* ctx, const float* logits, const float* logits0, const int64_t* target, int B,
+                         int h, int w, int S, float* iut_out, double* ce_out, float* iut0_out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits && logits0 && target && iut_out && iut0_out && B >= 1 && B <= 64 && h >= 1 && w >= 1 && S >= 1,
+            "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void* cnt;
+  int rc;
+  if ((rc = ensure_ws(ctx, "metrics.cnt", (size_t)B * 256 * (2 * 6 * 4 + 2 * 8) + 16, &cnt))) return rc;
+  return launch_seg_metrics(logits, target, B, h, w, S, iut_out, ce_out, (unsigned*)cnt, (hipStream_t)stream,
+                            logits0, iut0_out);
+}
+
+int cwt_seg_ce_fwd_bwd(cwt_ctx* ctx, const float* logits, const int64_t* target, int B, int h, int w, int S,
+                       float* loss_out, float* dlogits, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits && target && loss_out && dlogits && B >= 1, "bad arguments");
+  CWT_CHECK(S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1), "need S-1 == 8*(h-1) == 8*(w-1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void *lbl, *sc, *num;
+  int rc;
+  if ((rc = ensure_ws(ctx, "ce.lbl", (size_t)B * S * S, &lbl)) || (rc = ensure_ws(ctx, "ce.sc", 8192, &sc)) ||
+      (rc = ensure_ws(ctx, "ce.num", 64, &num)))
+    return rc;
+  return launch_seg_ce(logits, target, B, h, w, S, loss_out, dlogits, (uint8_t*)lbl, (AdaptScalars*)sc,
+                       (double*)num, (hipStream_t)stream);
+}
+
+int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int64_t n, int num_classes,
+                  int ignore_index, float* iut_out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(preds && target && iut_out && n >= 0 && num_classes >= 1 && num_classes <= 16, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  unsigned* cnt;
+  int rc;
+  if ((rc = ws(ctx, "iou.cnt", 3 * 16, &cnt))) return rc;
+  return launch_iou_preds(preds, target, n, num_classes, ignore_index, iut_out, cnt, (hipStream_t)stream);
+}
+
+int cwt_adapt_workgroups(cwt_ctx* ctx, int E, int n, int h, int w, int iters, int* G) {
+  if (!ctx || !G || E < 1 || n < 1 || h < 2 || w < 2) return fail(CWT_EARG, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  *G = adapt_persist_workgroups(E, n, h, w, iters, ctx->adapt_upw);
+  return 0;
+}
+
+int cwt_adapt_fuses_tail(cwt_ctx* ctx, int n, int h, int w, int iters, int* fused) {
+  if (!ctx || !fused || n < 1 || h < 2 || w < 2 || iters < 0) return fail(CWT_EARG, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  *fused = fused_tail_applies(ctx, n, h, w, iters) ? 1 : 0;
+  return 0;
+}
+
+int cwt_sgd_step(cwt_ctx* ctx, float* param, const float* grad, float* momentum_buf, int64_t n, float lr,
+                 float momentum, float weight_decay, int nesterov, int first_step, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(param && grad && n >= 0, "bad arguments");
+  CWT_CHECK(momentum == 0.f || momentum_buf, "momentum needs a buffer");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_sgd(param, grad, momentum_buf, n, lr, momentum, weight_decay, nesterov, first_step,
+                    (hipStream_t)stream);
+}
+
+}  // extern "C"

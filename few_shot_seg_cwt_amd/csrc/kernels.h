@@ -144,7 +144,6 @@ int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, s
 int launch_split_act(const float* x, long P, int C, int ld, __bf16* out, hipStream_t st);
 int launch_split_w3(const float* w, long R, int K, __bf16* ws, __bf16* wl, hipStream_t st);
 int launch_occupy(int nwg, int us, hipStream_t st);  // timing study (cwt_debug_occupy)
-int launch_unsplit_act(const __bf16* s, long P, int C, float* out, int ld, hipStream_t st);
 
 // inner loop (adapt.hip): cache of instantiated graphs of the 200-step launch sequence
 struct AdaptGraphCache {
@@ -258,5 +257,122 @@ int launch_norm_blend_bwd(const float* a, const float* b, const float* d, long T
 int launch_copy_2d(const float* src, long R, int Cc, long lds, float* dst, long ldd, hipStream_t st);
 int launch_mmn_blend_bwd(const float* d_fq, const float* d_mean, int B, long n, float att_wt, float* d_att,
                          float* d_fq_in, hipStream_t st);
+
+// ---- launchers the api*.hip units call, by defining unit (default arguments are written here only) ----
+struct AdaptScalars;
+struct AdaptDevArgs;
+struct FusedTail;  // tail_body.h
+
+// ---- conv_x3s.hip ----
+int launch_unsplit_act(const __bf16* s, long P, int C, float* out, int ld, hipStream_t st);
+int launch_widen_bf16(const __bf16* x, long n, float* y, hipStream_t st);
+
+// ---- adapt.hip ----
+int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int w, int S, float lr, int iters,
+                 float* W, float* f_ws, uint8_t* lbl_ws, AdaptScalars* sc, float* acc3, float* wbuf,
+                 AdaptDevArgs* dargs, AdaptGraphCache* cache, int upw, unsigned* status, long spin_limit,
+                 hipStream_t st, hipEvent_t ev_k0, hipEvent_t ev_k1, const FusedTail* tail = nullptr);
+const char* adapt_kernel_name(int E, int n, int h, int w, int iters, int upw);
+int adapt_persist_workgroups(int E, int n, int h, int w, int iters, int upw);
+extern unsigned long long* g_adapt_stamps;
+extern long g_adapt_stamps_n;
+size_t adapt_ws_sizes(int E, int n, int h, int w, int S, size_t* fws, size_t* lbl, size_t* sc, size_t* acc,
+                      size_t* wbuf, size_t* dargs);
+int launch_seg_ce(const float* logits, const int64_t* target, int B, int h, int w, int S, float* loss_out,
+                  float* dlogits, uint8_t* lbl_ws, AdaptScalars* sc, double* loss_num, hipStream_t st);
+
+// ---- seg.hip ----
+int launch_normalize(const float* f, int B, int Pb, float* out, const float* W0, float* logits0, hipStream_t st);
+int launch_classify(const float* W, const float* f, int B, int Pb, float* logits, hipStream_t st);
+int launch_classify_scaled(const float* W, const float* f, const float* inv, int B, int Pb, float* logits,
+                           hipStream_t st);
+int launch_classify_bwd(const float* dl, const float* f, int B, int Pb, float* dW, hipStream_t st);
+int launch_seg_metrics(const float* logits, const int64_t* target, int B, int h, int w, int S, float* iut,
+                       double* ce, unsigned* counts_ws, hipStream_t st, const float* logits2 = nullptr,
+                       float* iut2 = nullptr);
+int launch_iou_preds(const int64_t* preds, const int64_t* target, long n, int K, int ignore, float* iut,
+                     unsigned* counts_ws, hipStream_t st);
+// torch.optim.SGD step over a flat buffer
+int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first,
+               hipStream_t st);
+
+// ---- cwt_attn.hip ----
+size_t attention_fold_floats(int C, int H);
+int attention_fold(const float* w_qkvs, const float* fc_w, int C, int H, float* fold, float* ws, size_t ws_floats,
+                   hipStream_t st);
+size_t attention_infer_ws_floats(int B, int hw, int C, int H);
+int attention_infer(const float* q, const float* f, int B, int hw, int C, int H, const float* fold, const float* fc_b,
+                    const float* ln_w, const float* ln_b, float* out, float* inv_norm, float* logits0, float* ws,
+                    hipStream_t st);
+size_t attention_saved_floats(int B, int hw, int C, int H);
+size_t attention_ws_floats(int B, int hw, int C, int H);
+int attention_fwd(const float* q, const float* f, int B, int hw, int C, int H, const float* w_qkvs,
+                  const float* fc_w, const float* fc_b, const float* ln_w, const float* ln_b, float* out,
+                  float* saved, float* ws, hipStream_t st, float p_attn, float p_out, unsigned long long seed);
+int attention_bwd(const float* q, const float* f, int B, int hw, int C, int H, const float* w_qkvs,
+                  const float* fc_w, const float* fc_b, const float* ln_w, const float* ln_b, const float* saved,
+                  const float* d_out, float* g_w_qkvs, float* g_fc_w, float* g_fc_b, float* g_ln_w, float* g_ln_b,
+                  float* ws, hipStream_t st, float p_attn, float p_out, unsigned long long seed);
+size_t attention_bwd_ws_floats(int B, int hw, int C, int H);
+
+// ---- tail.hip ----
+size_t episode_tail_ws_floats(int B, int hw, int G);
+size_t episode_tail_cnt_words();
+unsigned episode_tail_max_epoch(int G);
+int launch_episode_tail(const float* q, const float* f, int B, int hw, int h, int w, int S, const int64_t* target,
+                        const float* fold, const float* fc_b, const float* ln_w, const float* ln_b, float* out,
+                        float* logits, float* logits0, float* iut, double* ce, float* iut0, float* ws,
+                        unsigned* cnt, unsigned epoch, int G, long spin_limit, unsigned* status, hipStream_t st,
+                        unsigned long long* stamps);
+
+// ---- heads.hip (variant heads) ----
+int launch_cos_weight(float* v, const float* g, int n, int C, int mode, float* w_eff, float* vnorm, hipStream_t st);
+int launch_cos_cls_fwd(const float* x, long P, int B, int n, const float* w_eff, const float* bias, const float* scale,
+                       float* out, hipStream_t st);
+int cos_cls_bwd_blocks(long total);
+int launch_cos_cls_bwd(const float* x, long P, int B, int n, const float* w_eff, const float* bias, const float* scale,
+                       const float* G, float* part, float* part_s, int mode, const float* v, const float* g,
+                       const float* vnorm, float* dv, float* dg, float* db, float* dscale, hipStream_t st);
+int launch_corr(const float* q, const float* k, int B, int Pq, int Pk, int C, float* qn, float* kn, float* sim,
+                hipStream_t st);
+int launch_gemm_abt(const float* A, const float* Bm, int B, int M, int N, int K, float* Cm, hipStream_t st);
+
+// ---- match.hip ----
+int launch_mutual_matching(const float* x, int B, int NA, int NB, int C, float* y, float* rowmax, float* colpart,
+                           float* colmax, hipStream_t st);
+int launch_mutual_matching_sum(const float* x, const float* x2, int B, int NA, int NB, float* y, float* rowmax,
+                               float* colpart, float* colmax, hipStream_t st);
+int launch_mutual_matching_planar2(const float* x, int B, int NA, int NB, float* y, float* rowmax, float* colpart,
+                                   float* colmax, hipStream_t st);
+int launch_cp4d_layer(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout, const float* Wa,
+                      const float* ba, const float* Wb, const float* bb, float* y, hipStream_t st);
+int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
+                              const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
+                              hipStream_t st);
+int launch_to_channels_last(const float* x, int B, int C, long P, float* y, hipStream_t st);
+int launch_add_inplace(float* y, const float* x, long n, hipStream_t st);
+int launch_match_softmax(const float* corr, int B, int NA, int NB, float temp, int ldp, float* P, hipStream_t st);
+int launch_match_vt(const float* v, int B, int NB, int C, int ldp, float* vt, hipStream_t st);
+int launch_cv4d_layer(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout, const float* W,
+                      const float* bias, int swap, float* y, hipStream_t st);
+int launch_sce_descriptor(const float* x, int B, int h, int w, int C, int k, int ldg, float* g, hipStream_t st);
+int launch_channel_sum(const float* x, int B, int L, long P, float* y, hipStream_t st);
+int launch_match_masks(float* corr, int B, int NA, int NB, const uint8_t* ig, const int64_t* s_mask, float* incons,
+                       int* q2k, float* pv, int* pi, hipStream_t st, float drop_p = 0.f, unsigned long long seed = 0);
+int launch_match_zero_ig_cols(float* g, const uint8_t* ig, int B, int NA, int NB, hipStream_t st);
+int launch_wa_attn(const float* tpg, int N, int h, int w, int co, const float* bt, const float* bp, const float* bg,
+                   float* wavg, hipStream_t st);
+int launch_wa_residual(const float* x, const float* back, const float* b, long n, int C, float* out, hipStream_t st);
+int launch_mmn_blend(const float* fq_in, const float* att, int B, long n, float att_wt, float* att_mean, float* fq_out,
+                     hipStream_t st);
+
+// ---- detr.hip ----
+int launch_linear_epilogue(const float* tmp, const float* bias, const float* acc, long P, int N, int relu, float* out,
+                           hipStream_t st);
+int launch_sine_pos_add(const float* x, int B, int h, int w, int C, float temperature, int normalize, float scale,
+                        float eps, float* out, hipStream_t st);
+int launch_deform_attn(const float* value, const float* offsets, const float* logits, int B, int H, int W, int M,
+                       int P, int D, float* out, hipStream_t st);
+int launch_norm_blend(const float* a, const float* b, long T, int C, float wt, float* out, hipStream_t st);
 
 }  // namespace cwt

@@ -1833,10 +1833,8 @@ int launch_mutual_matching(const float* x, int B, int NA, int NB, int C, float* 
   return 0;
 }
 
-// variant (cwt_debug_cp4d_layer): 0 the automatic choice, 1 never the rolling-window form, 2 only it
-int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
-                              const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
-                              hipStream_t st);
+// launch_cp4d_layer_variant's variant (cwt_debug_cp4d_layer): 0 the automatic choice, 1 never the rolling-window
+// form, 2 only it
 int launch_cp4d_layer(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout, const float* Wa,
                       const float* ba, const float* Wb, const float* bb, float* y, hipStream_t st) {
   return launch_cp4d_layer_variant(x, B, hA, wA, hB, wB, cin, cout, Wa, ba, Wb, bb, y, 0, st);

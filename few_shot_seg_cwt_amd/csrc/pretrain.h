@@ -98,8 +98,4 @@ int launch_seg_ce_smooth(PtLoss a, void* ws, size_t ws_bytes, float* loss, hipSt
 size_t seg_eval_ws_bytes(int N, int S, int w, int nc);
 int launch_seg_eval(PtLoss a, void* ws, size_t ws_bytes, float* out, float* iu, hipStream_t st);
 
-// torch.optim.SGD step over a flat buffer (seg.hip)
-int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first,
-               hipStream_t st);
-
 }  // namespace cwt

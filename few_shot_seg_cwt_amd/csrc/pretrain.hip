@@ -24,17 +24,11 @@
 #include "../../include/cwt.h"
 #include "../../include/cwt_debug.h"
 #include "common.h"
+#include "ctx.h"
 #include "kernels.h"
 #include "pretrain.h"
 
 namespace cwt {
-
-int ctx_device(const cwt_ctx* ctx);
-
-static const int kPtBlocks50[4] = {3, 4, 6, 3};
-static const int kPtBlocks101[4] = {3, 4, 23, 3};
-static const int kPtBins[4] = {1, 2, 3, 6};
-static inline int pt_down2(int x) { return (x - 1) / 2 + 1; }
 
 enum PtKind { PT_CONV = 0, PT_STEM1 = 1, PT_PLAIN = 2 };
 
@@ -172,7 +166,7 @@ static int pt_build(cwt_pretrain* pt) {
   B.conv(pt->stem[0], "layer0.0.weight", "layer0.1", 3, 64, 3, 2, 1, 1, true);
   B.conv(pt->stem[1], "layer0.3.weight", "layer0.4", 64, 64, 3, 1, 1, 1);
   B.conv(pt->stem[2], "layer0.6.weight", "layer0.7", 64, 128, 3, 1, 1, 1);
-  const int* nb = pt->layers == 50 ? kPtBlocks50 : kPtBlocks101;
+  const int* nb = pt->layers == 50 ? kBlocks50 : kBlocks101;
   const int planes_of[4] = {64, 128, 256, 512};
   int inplanes = 128;
   for (int li = 0; li < 4; ++li) {
@@ -430,7 +424,7 @@ struct PtStep {
 
 static int pt_ensure_acts(cwt_pretrain* pt, int N, int S) {
   if (pt->N == N && pt->S == S && pt->CAT) return 0;
-  const int Hs = pt_down2(S), H1 = pt_down2(Hs), h = pt_down2(H1);
+  const int Hs = down2(S), H1 = down2(Hs), h = down2(H1);
   pt->Hs = Hs;
   pt->H1 = H1;
   pt->h = h;
@@ -457,7 +451,7 @@ static int pt_ensure_acts(cwt_pretrain* pt, int N, int S) {
     for (int bi = 0; bi < (int)pt->blocks[li].size(); ++bi) {
       PtBlock& b = pt->blocks[li][bi];
       const std::string p = "l" + std::to_string(li) + "." + std::to_string(bi);
-      const int Ho = b.c2.stride == 2 ? pt_down2(H) : H;
+      const int Ho = b.c2.stride == 2 ? down2(H) : H;
       b.c1.Hi = H;
       b.c1.Ho = H;
       b.c2.Hi = H;
@@ -479,10 +473,10 @@ static int pt_ensure_acts(cwt_pretrain* pt, int N, int S) {
       H = Ho;
     }
   int ncells = 0;
-  for (int b : kPtBins) ncells += b * b;
+  for (int b : kBins) ncells += b * b;
   if ((rc = pt_ws(pt, "pool", (size_t)N * ncells * 2048 * 4, &pt->POOL))) return rc;
   for (int i = 0; i < 4; ++i)
-    if ((rc = act(pt->ppm[i], "ppm" + std::to_string(i), (long)N * kPtBins[i] * kPtBins[i], true))) return rc;
+    if ((rc = act(pt->ppm[i], "ppm" + std::to_string(i), (long)N * kBins[i] * kBins[i], true))) return rc;
   if ((rc = act(pt->bott, "bott", Mh, false))) return rc;
   if ((rc = pt_ws(pt, "fpre", (size_t)Mh * 512 * 4, &pt->Fpre)) || (rc = pt_ws(pt, "f", (size_t)Mh * 512 * 4, &pt->F)) ||
       (rc = pt_ws(pt, "logits", (size_t)Mh * pt->nc * 4, &pt->LOGITS)))
@@ -564,19 +558,19 @@ static int pt_forward(cwt_pretrain* pt, PtStep& s, const float* img, int train, 
   // interpolation weights times Q is the residual of the conv over the 2048 layer4 channels.
   PtConv& Bt = pt->bott;
   int ncells = 0;
-  for (int b : kPtBins) ncells += b * b;
+  for (int b : kBins) ncells += b * b;
   float *col, *Wq, *Q, *R, *Fld, *Wl;
   if ((rc = pt_ws(pt, "ppmcol", ((size_t)N * h * 16 * 2048 + (size_t)N * 16 * 16 * 2048) * 4, &col)) ||
       (rc = pt_ws(pt, "wq", (size_t)4 * 512 * 4608 * 4, &Wq)) ||
       (rc = pt_ws(pt, "q", (size_t)N * ncells * 4608 * 4, &Q)) ||
       (rc = pt_ws(pt, "r", (size_t)N * 12 * h * 3 * 512 * 4, &R)) || (rc = pt_ws(pt, "field", (size_t)Mh * 512 * 4, &Fld)) ||
       (rc = pt_ws(pt, "wl", (size_t)512 * 2048 * 9 * 4, &Wl)) ||
-      (rc = launch_ppm(pt->CAT, N, h, h, 2048, kPtBins, 4, col, pt->POOL, st, ACT_F32)) ||
+      (rc = launch_ppm(pt->CAT, N, h, h, 2048, kBins, 4, col, pt->POOL, st, ACT_F32)) ||
       (rc = launch_ppm_wq(pt->P + Bt.w_off, 4096 * 9, Wq, 0, st)))
     return rc;
   long base = 0;
   for (int i = 0; i < 4; ++i) {
-    const int b = kPtBins[i];
+    const int b = kBins[i];
     const long Mb = (long)N * b * b;
     PtConv& L = pt->ppm[i];
     const float* pool = pt->POOL + base * N * 2048;
@@ -588,7 +582,7 @@ static int pt_forward(cwt_pretrain* pt, PtStep& s, const float* img, int train, 
   }
   // bottleneck conv3x3 4096 -> 512 + BN + ReLU + Dropout2d (pspnet.py:124-129): the layer4
   // columns of the packed weights are a K prefix (packed_k's 32-channel blocks), copied dense
-  if ((rc = launch_ppm_field(Q, N, h, h, kPtBins, R, Fld, st))) return rc;
+  if ((rc = launch_ppm_field(Q, N, h, h, kBins, R, Fld, st))) return rc;
   CWT_HIP(hipMemcpy2DAsync(Wl, (size_t)2048 * 9 * 4, pt->P + Bt.w_off, (size_t)4096 * 9 * 4, (size_t)2048 * 9 * 4, 512,
                            hipMemcpyDeviceToDevice, st));
   if ((rc = s.conv_fwd(Bt, pt->CAT, N, h, 2048, Bt.y, 512, 6, Wl, 2048, 512, -1, -1, Fld, 512)) ||
@@ -633,7 +627,7 @@ static int pt_backward(cwt_pretrain* pt, PtStep& s, const float* dlogits) {
   // into the packed rows) and input gradient; the PPM columns through the field's adjoint
   PtConv& Bt = pt->bott;
   int ncells = 0;
-  for (int b : kPtBins) ncells += b * b;
+  for (int b : kBins) ncells += b * b;
   float *gWl, *gWq, *dQ, *R, *Wq;  // Wq: the forward's GEMM-form weights
   if ((rc = pt_ws(pt, "wq", (size_t)4 * 512 * 4608 * 4, &Wq)) || (rc = pt_ws(pt, "gwl", (size_t)512 * 2048 * 9 * 4, &gWl)) || (rc = pt_ws(pt, "gwq", (size_t)4 * 512 * 4608 * 4, &gWq)) ||
       (rc = pt_ws(pt, "dq", (size_t)N * ncells * 4608 * 4, &dQ)) || (rc = pt_ws(pt, "r", (size_t)N * 12 * h * 3 * 512 * 4, &R)))
@@ -641,7 +635,7 @@ static int pt_backward(cwt_pretrain* pt, PtStep& s, const float* dlogits) {
   if ((rc = s.bn_bwd(Bt, Mh, gA, 512, kReluFromY, 512, gY, nullptr, 0, (long)h * h, drop)) ||
       (rc = s.wgrad(Bt, gY, pt->CAT, 2048, N, h, 2048, gWl)) ||
       (rc = s.dgrad(Bt, gY, N, h, dcat, 2048, nullptr, 0, 6, 2048)) ||
-      (rc = launch_ppm_field_bwd(gY, N, h, h, kPtBins, R, dQ, s.st)))
+      (rc = launch_ppm_field_bwd(gY, N, h, h, kBins, R, dQ, s.st)))
     return rc;
   CWT_HIP(hipMemcpy2DAsync(pt->G + Bt.w_off, (size_t)4096 * 9 * 4, gWl, (size_t)2048 * 9 * 4, (size_t)2048 * 9 * 4, 512,
                            hipMemcpyDeviceToDevice, s.st));
@@ -651,7 +645,7 @@ static int pt_backward(cwt_pretrain* pt, PtStep& s, const float* dlogits) {
   if ((rc = pt_ws(pt, "dpool", (size_t)N * ncells * 2048 * 4, &dpool))) return rc;
   long base = 0;
   for (int i = 0; i < 4; ++i) {
-    const int b = kPtBins[i];
+    const int b = kBins[i];
     const long Mb = (long)N * b * b;
     PtConv& L = pt->ppm[i];
     const float* pool = pt->POOL + base * N * 2048;
@@ -665,7 +659,7 @@ static int pt_backward(cwt_pretrain* pt, PtStep& s, const float* dlogits) {
     base += b * b;
   }
   if ((rc = launch_ppm_wq(pt->G + Bt.w_off, 4096 * 9, gWq, 1, s.st)) ||
-      (rc = launch_avgpool_bwd(dpool, N, h, 2048, kPtBins, dcat, 2048, s.st)) ||
+      (rc = launch_avgpool_bwd(dpool, N, h, 2048, kBins, dcat, 2048, s.st)) ||
       (rc = capture("dcat", dcat, Mh, 2048, 2048)))
     return rc;
   // ResNet blocks in reverse (resnet.py:74-96)
@@ -732,9 +726,9 @@ int cwt_pretrain_create(cwt_ctx* ctx, int layers, int num_classes, int n_tensors
   if (layers != 50 && layers != 101) return fail(CWT_EARG, "layers must be 50 or 101");
   if (num_classes != 2 && num_classes != 16 && num_classes != 61)
     return fail(CWT_EARG, "num_classes_tr must be 2, 16 (PASCAL) or 61 (COCO)");
-  CWT_HIP(hipSetDevice(ctx_device(ctx)));
+  CWT_HIP(hipSetDevice(ctx->device));
   cwt_pretrain* pt = new cwt_pretrain();
-  pt->device = ctx_device(ctx);
+  pt->device = ctx->device;
   pt->layers = layers;
   pt->nc = num_classes;
   pt->eps = bn_eps;
@@ -1027,7 +1021,7 @@ int cwt_debug_pretrain_tensor(cwt_pretrain* pt, const char* name, float* host_ou
   } else if (nm.rfind("a:ppm", 0) == 0) {
     const int i = std::atoi(nm.c_str() + 5);
     if (i < 0 || i > 3) return fail(CWT_EARG, "no activation '" + nm + "'");
-    src = pt->ppm[i].a, rows = (long)pt->N * kPtBins[i] * kPtBins[i], cols = ld = 512;
+    src = pt->ppm[i].a, rows = (long)pt->N * kBins[i] * kBins[i], cols = ld = 512;
   } else if (nm.rfind("a:l", 0) == 0) {  // "a:l<layer>.<block>.c<1|2|3>": BN (+ residual) + ReLU output
     const int li = std::atoi(nm.c_str() + 3) - 1;
     const size_t d1 = nm.find('.'), d2 = nm.rfind(".c");
@@ -1083,10 +1077,10 @@ static float* dbg_ws(int device, size_t bytes) {
 extern "C" int cwt_debug_pretrain_op(cwt_ctx* ctx, int op, void* const* b, const int64_t* ia, const float* fa,
                                      void* stream) {
   if (!ctx || !b || !ia) return fail(CWT_EARG, "null argument");
-  CWT_HIP(hipSetDevice(ctx_device(ctx)));
+  CWT_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t wsf = (size_t)64 << 20;
-  float* ws = dbg_ws(ctx_device(ctx), wsf * 4);
+  float* ws = dbg_ws(ctx->device, wsf * 4);
   if (!ws) return fail(CWT_ESTATE, "debug workspace allocation failed");
   if (op == 0 || op == 1) {  // 0: weight gradient, 1: input gradient of a conv (ia: N Hi Ci Co k stride pad dil)
     const int N = (int)ia[0], Hi = (int)ia[1], Ci = (int)ia[2], Co = (int)ia[3], k = (int)ia[4], s = (int)ia[5],
@@ -1156,7 +1150,7 @@ extern "C" int cwt_debug_pretrain_op(cwt_ctx* ctx, int op, void* const* b, const
     // packed bottleneck weights [512][4096 * 9] (dW: only the PPM columns written), F / dF [N][h][h][512]
     const int N = (int)ia[0], h = (int)ia[1];
     int ncells = 0;
-    for (int bb : kPtBins) ncells += bb * bb;
+    for (int bb : kBins) ncells += bb * bb;
     float* Wq = ws;
     float* gWq = Wq + (size_t)4 * 512 * 4608;
     float* Q = gWq + (size_t)4 * 512 * 4608;
@@ -1188,23 +1182,23 @@ extern "C" int cwt_debug_pretrain_op(cwt_ctx* ctx, int op, void* const* b, const
     if ((rc = launch_ppm_wq((float*)b[4], 4096 * 9, Wq, 0, st))) return rc;
     long base = 0;
     for (int i = 0; i < 4; ++i) {
-      const int Mb = N * kPtBins[i] * kPtBins[i];
+      const int Mb = N * kBins[i] * kBins[i];
       if ((rc = gemm(P + base * N * 512, 512, 1, Wq + (size_t)i * 512 * 4608, 4608, 1, Q + base * N * 4608, 4608, Mb,
                      4608, 512)))
         return rc;
-      base += kPtBins[i] * kPtBins[i];
+      base += kBins[i] * kBins[i];
     }
-    if ((rc = launch_ppm_field(Q, N, h, h, kPtBins, R, (float*)b[2], st)) ||
-        (rc = launch_ppm_field_bwd((const float*)b[1], N, h, h, kPtBins, R, dQ, st)))
+    if ((rc = launch_ppm_field(Q, N, h, h, kBins, R, (float*)b[2], st)) ||
+        (rc = launch_ppm_field_bwd((const float*)b[1], N, h, h, kBins, R, dQ, st)))
       return rc;
     base = 0;
     for (int i = 0; i < 4; ++i) {
-      const int Mb = N * kPtBins[i] * kPtBins[i];
+      const int Mb = N * kBins[i] * kBins[i];
       const float* dQb = dQ + base * N * 4608;
       if ((rc = gemm(dQb, 4608, 1, Wq + (size_t)i * 512 * 4608, 1, 4608, dP + base * N * 512, 512, Mb, 512, 4608)) ||
           (rc = gemm(P + base * N * 512, 1, 512, dQb, 4608, 1, gWq + (size_t)i * 512 * 4608, 4608, 512, 4608, Mb)))
         return rc;
-      base += kPtBins[i] * kPtBins[i];
+      base += kBins[i] * kBins[i];
     }
     return launch_ppm_wq((float*)b[5], 4096 * 9, gWq, 1, st);
   }

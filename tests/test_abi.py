@@ -106,3 +106,12 @@ def test_library_provenance_is_the_tree(lib):
     assert lib.cwt_version().decode().endswith("src=" + build.source_hash())
     with pytest.raises(L.CwtError, match="stale"):
         L.check_provenance("libcwt 0.2 (gfx950) src=0000000000000000", "libcwt.so")
+
+
+def test_build_lists_cover_every_source_file():
+    """Every .hip / .h / .inc under csrc/ is in build.SOURCES or build.HEADERS, and nothing else is: a
+    file missing from the lists would be left out of source_hash, and a stale library would load."""
+    listed = build.SOURCES + build.HEADERS
+    assert len(set(listed)) == len(listed), sorted(f for f in set(listed) if listed.count(f) > 1)
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".h", ".inc"))}
+    assert on_disk == set(listed), (sorted(on_disk - set(listed)), sorted(set(listed) - on_disk))

@@ -23,7 +23,7 @@ from few_shot_seg_cwt_amd import _lib  # noqa: E402
 
 def shapes(layers, S, N):
     """(name, count, Ci, Co, Hi, k, stride, dil, res) of the implicit-GEMM convs of one
-    extractor pass (api.hip run_extract; resnet.py:57-96 blocks with pspnet.py:124-129's
+    extractor pass (api_extract.hip run_extract; resnet.py:57-96 blocks with pspnet.py:124-129's
     dilation surgery, the PPM-folded bottleneck conv), identical shapes merged."""
     if layers == 0:   # the variant heads' GEMMs as 1x1 convs over an S x S map (MMN WeightAverage
         # theta|phi|g and conv_back, forward and the backward's row-major products; config 0:60:1)

@@ -81,7 +81,7 @@ def main(path, pmc_path=None):
     out.append("")
     out.append(f"Stack: {tot_t:.0f} us of launches, floor {tot_floor:.0f} us, roofline_frac {tot_floor / tot_t:.3f}")
     # the Winograd forms on the work they execute: each x6w record is followed by
-    # its wino_in / wino_gemm / wino_out sub-records (api.hip run_wino_conv)
+    # its wino_in / wino_gemm / wino_out sub-records (api_extract.hip run_wino_conv)
     wrows = []
     prows = d.get("winograd_parts", rows)   # bench.py's level-3 extraction (the parts' own events)
     for i, r in enumerate(prows):
