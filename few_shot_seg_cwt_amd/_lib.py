@@ -121,6 +121,10 @@ SIGNATURES = {
                                _I, _I, _P]),
     "cwt_debug_conv_x6w": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I,
                                 _I, _I, _P]),
+    "cwt_debug_conv_x6_dual": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P,
+                                    _I, _I, _I, _P]),
+    "cwt_debug_wino_in": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cwt_debug_splitk_epilogue": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "cwt_debug_conv_form": (_I, [_I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_conv_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_census": (_I, [_P, _I, _P, _P]),

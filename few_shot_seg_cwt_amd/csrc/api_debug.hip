@@ -280,6 +280,86 @@ int cwt_debug_conv_x6(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int C
                       relu, y, y_ld, y_off, nullptr, bm, bn, nsplit, stream);
 }
 
+int cwt_debug_conv_x6_dual(cwt_ctx* ctx, const float* t, int N, int Ho, int Wo, int K1, const float* x, int Hi2,
+                           int Wi2, int K2, int stride2, const float* w3, const float* s3, const float* b3,
+                           const float* wd, const float* sd, const float* bd, int Co, int relu, float* y, int bm,
+                           int bn, int nsplit, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(t && x && w3 && s3 && b3 && wd && sd && bd && y, "null buffer");
+  CWT_CHECK(N >= 1 && Ho >= 1 && Wo >= 1 && K1 > 0 && K2 > 0 && K1 % 32 == 0 && K2 % 32 == 0 && Co % 64 == 0,
+            "need K1 % 32 == 0, K2 % 32 == 0, Co % 64 == 0");
+  CWT_CHECK(stride2 >= 1 && (Ho - 1) * stride2 < Hi2 && (Wo - 1) * stride2 < Wi2, "second source too small");
+  const int K = K1 + K2;
+  ConvSArgs a = conv_s_geom(N, Ho, Wo, K1, Co, 1, 1, 0, 1);
+  int rc;
+  ConvPlan p = plan_conv_dual(a.M, Co, K);
+  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &p))) return rc;  // before any device call
+  if (nsplit > 0) {
+    p.kt_per_split = cdiv(K / 32, nsplit);
+    p.nsplit = cdiv(K / 32, p.kt_per_split);
+  }
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  float *wf, *shf, *ones, *part = nullptr;
+  __bf16 *w3s, *w3l;
+  if ((rc = zero_line(ctx, &a.zero)) || (rc = ws(ctx, "dbg.dual.w", (size_t)Co * K, &wf)) ||
+      (rc = ws(ctx, "dbg.dual.sh", (size_t)Co, &shf)) || (rc = ws(ctx, "dbg.dual.ones", (size_t)Co, &ones)) ||
+      (rc = ws(ctx, "dbg.dual.w3s", (size_t)Co * K * 2, &w3s)) || (rc = ws(ctx, "dbg.dual.w3l", (size_t)Co * K, &w3l)))
+    return rc;
+  // CWT_DBG_W3_CACHE=1 (timing tools): fold and split the weights only when their source or shape changes
+  static const bool w3_cache = getenv("CWT_DBG_W3_CACHE") && getenv("CWT_DBG_W3_CACHE")[0] == '1';
+  static const void* f_src = nullptr;
+  static long f_n = 0;
+  static void* f_dst = nullptr;
+  if (!(w3_cache && f_src == w3 && f_n == (long)Co * K && f_dst == w3s)) {
+    const std::vector<float> one(Co, 1.0f);
+    CWT_HIP(hipMemcpyAsync(ones, one.data(), sizeof(float) * Co, hipMemcpyHostToDevice, st));
+    CWT_HIP(hipStreamSynchronize(st));
+    if ((rc = launch_fold_dual(w3, s3, b3, K1, wd, sd, bd, K2, Co, wf, shf, st)) ||
+        (rc = launch_split_w3(wf, Co, K, w3s, w3l, st)))
+      return rc;
+    f_src = w3;
+    f_n = (long)Co * K;
+    f_dst = w3s;
+  }
+  a.K = K;
+  a.xs = (const __bf16*)t;
+  a.xs2 = (const __bf16*)x;
+  a.Hi2 = Hi2;
+  a.Wi2 = Wi2;
+  a.Ci2 = K2;
+  a.stride2 = stride2;
+  a.kt_switch = K1 / 32;
+  a.ws = w3s;
+  a.ws_lo = w3l;
+  a.scale = ones;
+  a.shift = shf;
+  a.relu = relu;
+  a.y = y;
+  a.y_ld = Co;
+  const size_t pf = (size_t)p.nsplit * a.M * Co;
+  if (p.nsplit > 1 && (rc = ws(ctx, "dbg.PART", pf, &part))) return rc;
+  return launch_conv_x3s(a, p, 0, part, pf, st, 6);
+}
+
+int cwt_debug_wino_in(cwt_ctx* ctx, const float* x, int nsplit, const float* scale, const float* shift, int relu,
+                      int N, int H, int W, int C, int d, int m, float* V, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && V && N >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && d >= 1 && (m == 2 || m == 4), "wino_in");
+  CWT_CHECK(nsplit == 0 || (scale && shift && nsplit <= 64), "wino_in: split-K partials need scale and shift");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const WinoGeom g = wino_geom(N, H, W, d, m);
+  return nsplit > 0 ? launch_wino_in_splitk(x, nsplit, scale, shift, relu, g, C, V, (hipStream_t)stream)
+                    : launch_wino_in(x, g, C, V, (hipStream_t)stream);
+}
+
+int cwt_debug_splitk_epilogue(cwt_ctx* ctx, const float* part, int nsplit, int M, int Co, const float* scale,
+                              const float* shift, int relu, float* y, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_HIP(hipSetDevice(ctx->device));
+  return launch_splitk_reduce_f32(part, nsplit, M, Co, scale, shift, relu, y, (hipStream_t)stream);
+}
+
 int cwt_debug_conv_form(int prec, int bm, int bn, int var, int* out4) {
   CWT_CHECK(out4, "out4 is NULL");
   const ConvForm* f = find_conv_form(prec, bm, bn, var);

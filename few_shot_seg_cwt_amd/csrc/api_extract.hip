@@ -13,6 +13,10 @@ namespace cwt {
 struct Block {
   ConvLayer c1, c2, c3, down;
   bool has_down = false;
+  // has_down, x6: conv3 + BN and the downsample conv + BN as ONE 1x1 GEMM over the concatenated K
+  // (fold_down): w / w_s / w_l the folded rows [s3 W3 | sd Wd], Ci = c3.Ci (the first source's),
+  // unit scale, shift b3 + bd
+  ConvLayer fused;
 };
 
 struct Backbone {  // the opaque cwt_backbone of the C ABI
@@ -228,6 +232,44 @@ static int load_ppm_fold(Backbone* bb, const HostParams& hp, float eps) {
   return 0;
 }
 
+// The declared exact shortcut of a block with a downsample branch: both branches are
+// 1x1 convs onto the same M x Co output, each followed by an eval-mode BN (a per-channel affine), so
+//   relu(bn3(conv3(t)) + bnd(convd(x))) = relu([t | x] . [s3 W3 ; sd Wd]^T + (b3 + bd)).
+// (Re)builds b.fused's rows from the two layers' current eval folds, then the x6 split; the folds
+// change with the BN running statistics, so a training-mode BN pass calls this again.
+static int fold_down(const Block& b, hipStream_t st) {
+  const int K1 = b.c3.Ci, K2 = b.down.Ci, Co = b.c3.Co;
+  int rc = launch_fold_dual(b.c3.w, b.c3.scale, b.c3.shift, K1, b.down.w, b.down.scale, b.down.shift, K2, Co,
+                            b.fused.w, b.fused.shift, st);
+  if (!rc) rc = launch_split_w3(b.fused.w, Co, K1 + K2, b.fused.w_s, b.fused.w_l, st);
+  return rc;
+}
+
+static int alloc_fused(Backbone* bb, Block* b) {
+  const size_t n = (size_t)b->c3.Co * (b->c3.Ci + b->down.Ci);
+  void *w = nullptr, *s = nullptr, *l = nullptr, *sh = nullptr;
+  CWT_HIP(hipMalloc(&w, n * 4));
+  bb->allocs.push_back(w);
+  CWT_HIP(hipMalloc(&s, n * 4));
+  bb->allocs.push_back(s);
+  CWT_HIP(hipMalloc(&l, n * 2));
+  bb->allocs.push_back(l);
+  CWT_HIP(hipMalloc(&sh, (size_t)b->c3.Co * 4));
+  bb->allocs.push_back(sh);
+  ConvLayer& F = b->fused;
+  F.Ci = b->c3.Ci;
+  F.Co = b->c3.Co;
+  F.w = (float*)w;
+  F.w_s = (__bf16*)s;
+  F.w_l = (__bf16*)l;
+  F.scale = bb->ones;
+  F.shift = (float*)sh;
+  const int rc = fold_down(*b, nullptr);
+  if (rc) return rc;
+  CWT_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
 static int load_backbone(int layers, const HostParams& hp, float eps, Backbone** out) {
   if (layers != 50 && layers != 101) return fail(CWT_EARG, "layers must be 50 or 101");
   Backbone* bb = new Backbone();
@@ -294,6 +336,12 @@ static int load_backbone(int layers, const HostParams& hp, float eps, Backbone**
     cleanup();
     return rc;
   }
+  for (int li = 0; li < 4; ++li)
+    for (Block& b : bb->blocks[li])
+      if (b.has_down && (rc = alloc_fused(bb, &b))) {
+        cleanup();
+        return rc;
+      }
   *out = bb;
   return 0;
 }
@@ -363,11 +411,12 @@ int force_conv_form(int prec, int bm, int bn, int Co, ConvPlan* p) {
 // matrix-core arithmetic (wino.hip): input transform -> P = (m+2)^2 batched GEMMs
 // (conv_igemm_x6, batch P) -> output transform with the conv's BN / residual / ReLU.  us / ul: the
 // layer's wino_s / wino_l (m = 2) or wino4_s / wino4_l (m = 4); bm > 0 overrides the GEMMs' tile
-// (bm = 1000 * variant + rows, as cwt_debug_conv_s).
+// (bm = 1000 * variant + rows, as cwt_debug_conv_s).  sk: x holds the split-K partial planes of the
+// 1x1 conv that produces this conv's input, reduced inside the input transform (ctx.h).
 int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int Ci, int Co, int d, int m,
                          const __bf16* us, const __bf16* ul, const float* scale, const float* shift, const float* res,
                          int res_ld, int relu, float* y, int y_ld, int y_off, int stage, hipStream_t st, int bm,
-                         int bn) {
+                         int bn, const WinoSplitKSrc* sk) {
   if (m != 2 && m != 4) return fail(CWT_EARG, "winograd: output tile must be 2 or 4");
   const WinoGeom g = wino_geom(N, H, W, d, m);
   if (g.T * Ci * 4 >= (1L << 31) || g.T * Co * 4 >= (1L << 31)) return fail(CWT_EARG, "winograd: plane too large");
@@ -386,8 +435,9 @@ int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int Ci, int
   (void)stage;
   const double vb = 4.0 * g.P * g.T * Ci, mb = 4.0 * g.P * g.T * Co;
   Prof pin(ctx, st, "wino_in " + std::to_string(Ci) + "@" + std::to_string(H), 0.0,
-           4.0 * N * H * W * Ci + vb, plev);
-  rc = launch_wino_in(x, g, Ci, V, st);
+           4.0 * N * H * W * Ci * (sk ? sk->nsplit : 1) + vb, plev);
+  rc = sk ? launch_wino_in_splitk(x, sk->nsplit, sk->scale, sk->shift, sk->relu, g, Ci, V, st)
+          : launch_wino_in(x, g, Ci, V, st);
   pin.end();
   if (rc) return rc;
   ConvSArgs a = conv_s_geom(1, (int)g.T, 1, Ci, Co, 1, 1, 0, 1);  // each GEMM: a 1x1 conv over the T tiles
@@ -448,6 +498,15 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
   const bool f32ops = f32d || x6;  // fp32 NHWC operands on the LDS-DMA body
   const bool dma = s_path || f32ops;  // conv_x3s.hip kernels
   const int prec = b16 ? 1 : conv_split ? 3 : x6 ? 6 : 0;
+  // x6 (eval mode) only, A/B knobs read per call: CWT_FUSE_DOWN=0 restores the downsample conv as a
+  // launch of its own (through D), CWT_FUSE_SPLITK_WINO=0 the split-K epilogue launch in front of a
+  // Winograd conv
+  const auto knob_on = [](const char* name) {
+    const char* v = getenv(name);
+    return !(v && v[0] == '0');
+  };
+  const bool fuse_down = x6 && knob_on("CWT_FUSE_DOWN");
+  const bool fuse_splitk = x6 && knob_on("CWT_FUSE_SPLITK_WINO");
   const int Hs = down2(S), H1 = down2(Hs), h = down2(H1);
   const long sA = std::max({(long)N * Hs * Hs * 128, (long)N * H1 * H1 * 256, (long)N * h * h * 2048});
   const long sT1 = std::max((long)N * H1 * H1 * 128, (long)N * h * h * 512);
@@ -500,12 +559,22 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
       cc(&blk.c2, T1, N, H, H, blk.c2.Ci, T2, blk.c2.Co, 0, nullptr, 0, 1);
       const float* res = cur;
       int res_ld = Cin;
-      if (blk.has_down) {
-        cc(&blk.down, cur, N, H, H, Cin, D, blk.down.Co, 0, nullptr, 0, 0);
-        res = D;
-        res_ld = blk.down.Co;
+      if (blk.has_down && fuse_down) {  // conv3 + downsample conv as one two-source GEMM (fold_down)
+        cc(&blk.fused, T2, N, Ho, Ho, blk.c3.Ci, other, blk.c3.Co, 0, nullptr, 0, 1);
+        ConvCall& c = calls.back();
+        c.x2 = cur;
+        c.Hi2 = c.Wi2 = H;
+        c.Ci2 = Cin;
+        c.stride2 = blk.down.stride;
+        args.back().K += Cin;
+      } else {
+        if (blk.has_down) {
+          cc(&blk.down, cur, N, H, H, Cin, D, blk.down.Co, 0, nullptr, 0, 0);
+          res = D;
+          res_ld = blk.down.Co;
+        }
+        cc(&blk.c3, T2, N, Ho, Ho, blk.c3.Ci, other, blk.c3.Co, 0, res, res_ld, 1);
       }
-      cc(&blk.c3, T2, N, Ho, Ho, blk.c3.Ci, other, blk.c3.Co, 0, res, res_ld, 1);
       if (bi == nbk - 1) last_of_layer[li] = calls.size() - 1;
       std::swap(cur, other);
       H = Ho;
@@ -523,7 +592,9 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
   for (size_t i = 0; i < calls.size(); ++i) {
     const ConvArgs& a = args[i];
     if (b16 && !calls[i].L->w_b) return fail(CWT_ESTATE, "bf16 conv weights missing (Ci % 64 != 0)");
-    ConvPlan pl = dma ? plan_conv_s(prec, a.M, a.Co, a.K) : plan_conv(a.M, a.Co, a.K);
+    ConvPlan pl = calls[i].x2 ? plan_conv_dual(a.M, a.Co, a.K)
+                  : dma       ? plan_conv_s(prec, a.M, a.Co, a.K)
+                              : plan_conv(a.M, a.Co, a.K);
     plans.push_back(pl);
     if (pl.nsplit > 1) part_floats = std::max(part_floats, (size_t)pl.nsplit * a.M * a.Co);
   }
@@ -567,6 +638,24 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
     return (c.L->wino_s || c.L->wino4_s) && c.L->k == 3 && c.L->stride == 1 && c.L->pad == c.L->dil &&
            c.x_ld == c.L->Ci;
   };
+  // the Winograd output tile call i takes (0: the direct conv)
+  // A/B: CWT_WINO=0 every conv direct, 2 / 4 every Winograd-eligible conv in F(2x2) / F(4x4)
+  static const int wino_env = getenv("CWT_WINO") && getenv("CWT_WINO")[0] ? atoi(getenv("CWT_WINO")) : -1;
+  auto wino_tile = [&](size_t i) {
+    const ConvArgs& a = args[i];
+    int wm = x6 && wino_env != 0 && c_wino(calls[i])
+                 ? (wino_env == 2 || wino_env == 4 ? wino_env : wino_tile_default(a.Ci, a.Co, a.dil, a.Ho))
+                 : 0;
+    if (wm && !(wm == 4 ? calls[i].L->wino4_s : calls[i].L->wino_s)) wm = 0;  // form not built for this layer
+    return wm;
+  };
+  // call i leaves its split-K partials unreduced for call i + 1's input transform: a split-K conv
+  // into T1 (a block's conv1: read by its conv2 alone, never a mid feature) in front of a Winograd conv
+  auto partials_to_wino = [&](size_t i) {
+    return fuse_splitk && i + 1 < n_backbone_calls && plans[i].nsplit > 1 && calls[i].y == T1 && !calls[i].res &&
+           calls[i].y_off == 0 && calls[i].y_ld == args[i].Co && calls[i + 1].x == T1 && !wino_tile(i) &&
+           wino_tile(i + 1) != 0;
+  };
   auto run_call = [&](size_t i) -> int {
     ConvArgs a = args[i];  // a copy: the training-mode BN override below
     // training-mode BN: raw conv (scale 1, shift 0); the bottleneck keeps its residual (the
@@ -578,13 +667,9 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
       a.relu = 0;
       if (!keep_res) a.res = nullptr;
     }
-    // A/B: CWT_WINO=0 every conv direct, 2 / 4 every Winograd-eligible conv in F(2x2) / F(4x4)
-    static const int wino_env = getenv("CWT_WINO") && getenv("CWT_WINO")[0] ? atoi(getenv("CWT_WINO")) : -1;
-    int wm = x6 && wino_env != 0 && c_wino(calls[i])
-                 ? (wino_env == 2 || wino_env == 4 ? wino_env : wino_tile_default(a.Ci, a.Co, a.dil, a.Ho))
-                 : 0;
-    if (wm && !(wm == 4 ? calls[i].L->wino4_s : calls[i].L->wino_s)) wm = 0;  // form not built for this layer
+    const int wm = wino_tile(i);
     const bool wino = wm != 0;
+    const bool part_out = partials_to_wino(i), part_in = i > 0 && partials_to_wino(i - 1);
     // the Winograd form's record names its batched GEMM's plan; its FLOPs stay the direct conv's
     // (algorithmic: the roofline prices the conv, not the form that computes it)
     const WinoGeom wg = wino_geom(a.N, a.Hi, a.Wi, a.dil, wm ? wm : 2);
@@ -593,7 +678,9 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
     // algorithmic bytes: every operand once; 4 B per element (fp32 or the bf16x3 S-layout),
     // 2 B for the bf16 stack's activations and weights (its fp32 bottleneck output: 4 B)
     const double eb = b16 ? 2.0 : 4.0, ob = calls[i].out_f32 ? 4.0 : eb;
-    const double bytes = eb * ((double)a.N * a.Hi * a.Wi * a.Ci + (double)a.Co * a.K) +
+    const ConvCall& cl = calls[i];
+    const double bytes = eb * ((double)a.N * a.Hi * a.Wi * a.Ci + (double)a.N * cl.Hi2 * cl.Wi2 * cl.Ci2 +
+                               (double)a.Co * a.K) +
                          ob * ((double)a.M * a.Co + (a.res ? (double)a.M * a.Co : 0.0));
     Prof p(ctx, st,
            std::string(b16 ? "conv_igemm_b16<" : conv_split ? "conv_igemm_x3s<" : wino ? (wm == 4 ? "conv_igemm_x6w4<" : "conv_igemm_x6w<")
@@ -602,15 +689,19 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
                std::to_string(pl.bn) + "," +
                std::to_string(calls[i].stage) + ">" +
                (pl.nsplit > 1 ? "+splitk" + std::to_string(pl.nsplit) : std::string()) + " " +
-               std::to_string(a.Ci) + "x" + std::to_string(a.Co) + "k" + std::to_string(a.kh) + "s" +
+               std::to_string(a.Ci) + (cl.x2 ? "+" + std::to_string(cl.Ci2) : std::string()) + "x" +
+               std::to_string(a.Co) + "k" + std::to_string(a.kh) + "s" +
                std::to_string(a.stride) + "d" + std::to_string(a.dil) + "@" + std::to_string(a.Ho),
            flops, bytes, calls[i].stage == 6 ? 1 : 2);
     int r;
     if (wino) {
       const ConvCall& c = calls[i];
-      r = run_wino_conv(ctx, c.x, a.N, a.Hi, a.Wi, a.Ci, a.Co, a.dil, wm, wm == 4 ? c.L->wino4_s : c.L->wino_s,
-                        wm == 4 ? c.L->wino4_l : c.L->wino_l, a.scale, a.shift, a.res, c.res_ld, a.relu, c.y, c.y_ld,
-                        c.y_off, c.stage, st);
+      // its input still in the previous call's split-K partials: reduced by the input transform
+      const WinoSplitKSrc sk{part_in ? plans[i - 1].nsplit : 0, part_in ? calls[i - 1].L->scale : nullptr,
+                             part_in ? calls[i - 1].L->shift : nullptr, part_in ? calls[i - 1].relu : 0};
+      r = run_wino_conv(ctx, part_in ? PART : c.x, a.N, a.Hi, a.Wi, a.Ci, a.Co, a.dil, wm,
+                        wm == 4 ? c.L->wino4_s : c.L->wino_s, wm == 4 ? c.L->wino4_l : c.L->wino_l, a.scale, a.shift,
+                        a.res, c.res_ld, a.relu, c.y, c.y_ld, c.y_off, c.stage, st, 0, 0, part_in ? &sk : nullptr);
     } else if (dma) {
       ConvSArgs sa = conv_s_geom(a.N, a.Hi, a.Wi, a.Ci, a.Co, a.kh, a.stride, a.pad, a.dil);
       const ConvCall& c = calls[i];
@@ -631,7 +722,17 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
         sa.res_s = (const __bf16*)a.res;
       }
       sa.relu = a.relu;
-      r = launch_conv_x3s(sa, pl, c.stage, PART, part_floats, st, prec);
+      if (c.x2) {
+        sa.xs2 = (const __bf16*)c.x2;
+        sa.Hi2 = c.Hi2;
+        sa.Wi2 = c.Wi2;
+        sa.Ci2 = c.Ci2;
+        sa.stride2 = c.stride2;
+        sa.kt_switch = a.Ci / 32;
+        sa.K = a.K;
+      }
+      r = part_out ? launch_conv_x3s_partials(sa, pl, c.stage, PART, part_floats, st, prec)
+                   : launch_conv_x3s(sa, pl, c.stage, PART, part_floats, st, prec);
     } else {
       r = launch_conv(a, pl, calls[i].stage, PART, part_floats, st);
     }
@@ -742,6 +843,10 @@ static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N
   if (!rc && tb)  // refold the bottleneck's new eval BN scale into the PPM-branch weights
     for (int i = 0; i < 4 && !rc; ++i)
       rc = launch_scale_cols(bb->ppm_q_raw[i], bb->ppm_q[i], 512L * 4608, 512, bb->bott.scale, st);
+  if (!rc && tb)  // ... and the new conv3 / downsample eval folds into the fused rows
+    for (int li = 0; li < 4 && !rc; ++li)
+      for (const Block& b : bb->blocks[li])
+        if (b.has_down && !rc) rc = fold_down(b, st);
   return rc;
 }
 

@@ -201,4 +201,27 @@ int launch_scale_cols(const float* src, float* dst, long n, int period, const fl
   return 0;
 }
 
+// Folded rows of a block's conv3 + downsample conv as one GEMM over the concatenated K (each product
+// rounded once, in fp32) and the summed BN shift; rebuilt after a training-mode BN pass like ppm_q
+__global__ void fold_dual_kernel(const float* __restrict__ w3, const float* __restrict__ s3,
+                                 const float* __restrict__ b3, int K1, const float* __restrict__ wd,
+                                 const float* __restrict__ sd, const float* __restrict__ bd, int K2, int Co,
+                                 float* __restrict__ out, float* __restrict__ shift_out) {
+  const int K = K1 + K2;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)Co * K) return;
+  const int co = (int)(i / K), k = (int)(i - (long)co * K);
+  out[i] = k < K1 ? w3[(long)co * K1 + k] * s3[co] : wd[(long)co * K2 + (k - K1)] * sd[co];
+  if (k == 0) shift_out[co] = b3[co] + bd[co];
+}
+
+int launch_fold_dual(const float* w3, const float* s3, const float* b3, int K1, const float* wd, const float* sd,
+                     const float* bd, int K2, int Co, float* out, float* shift_out, hipStream_t st) {
+  const long n = (long)Co * (K1 + K2);
+  hipLaunchKernelGGL(fold_dual_kernel, dim3(cdiv(n, 256L)), dim3(256), 0, st, w3, s3, b3, K1, wd, sd, bd, K2, Co, out,
+                     shift_out);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace cwt

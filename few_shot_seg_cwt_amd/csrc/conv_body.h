@@ -243,9 +243,27 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
   // a row past M gets an offset past the buffer's end, which the hardware reads as zeros (no zero
   // line, no 64-bit address math, no exec-masked branch per piece).  The weights' K offset goes in
   // the uniform soffset.
-  __amdgpu_buffer_rsrc_t rsA, rsB, rsL;
-  int a_roff[LA], b_voff[LB], l_voff[LBL > 0 ? LBL : 1];
+  // PF & 128 (x6 1x1 convs, with PF & 8): a second A source behind its own resource (ConvSArgs::xs2).
+  // Its rows' constant offsets come from its own geometry; which source a K-tile reads is uniform, and
+  // both sources give the same piece count per tile, so the counted vmcnt scheme holds unchanged.
+  constexpr bool DUAL = (PF & 128) != 0;
+  static_assert(!DUAL || (PREC == 6 && (PF & 8) != 0), "dual A source: x6 with buffer addressing");
+  __amdgpu_buffer_rsrc_t rsA, rsB, rsL, rsA2;
+  int a_roff[LA], b_voff[LB], l_voff[LBL > 0 ? LBL : 1], a_roff2[DUAL ? LA : 1];
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer builtins exist for the device pass only
+  if constexpr (DUAL) {
+    const int cbl2 = a.Ci2 >> 5;
+    rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.xs2, (short)0, (int)((long)a.N * a.Hi2 * a.Wi2 * cbl2 * 128),
+                                             0x00020000);
+#pragma unroll
+    for (int j = 0; j < LA; ++j) {
+      const int m = m0 + (wv * LA + j) * 8 + lrow;
+      const int n = m / HoWo, rem = m - n * HoWo;
+      const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
+      const int pix2 = (n * a.Hi2 + oh * a.stride2) * a.Wi2 + ow * a.stride2;
+      a_roff2[j] = m < a.M ? (pix2 * cbl2 * 64 + a_ch[j]) * 2 : (int)0x80000000;  // rows past M read zeros
+    }
+  }
   if constexpr ((PF & 8) != 0) {
     const int cbl = a.Ci >> (PREC == 1 ? 6 : 5);
     const long a_bytes = (long)a.N * a.Hi * a.Wi * cbl * 128;
@@ -276,12 +294,25 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
     if constexpr ((PF & 8) != 0) {
       const int dy = i_ky * a.dil, dx = i_kx * a.dil;
       const int uni = ((dy * a.Wi + dx) * cblocks + i_cb) * 128;
+      bool second = false;  // uniform: the tile's source
+      if constexpr (DUAL) {
+        second = i_kt >= a.kt_switch;
+        if (second) {
+          const unsigned uni2 = (unsigned)(i_kt - a.kt_switch) * 128u;  // (a past-the-end offset stays past it)
 #pragma unroll
-      for (int j = 0; j < LA; ++j) {
-        const int ih = a_ih0[j] + dy, iw = a_iw0[j] + dx;
-        const bool in = (unsigned)ih < (unsigned)a.Hi && (unsigned)iw < (unsigned)a.Wi;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (CWT_LDS void*)(sb + (wv * LA + j) * 1024), 16,
-                                                 in ? a_roff[j] + uni : (int)0x80000000, 0, 0, 0);
+          for (int j = 0; j < LA; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA2, (CWT_LDS void*)(sb + (wv * LA + j) * 1024), 16,
+                                                     (int)((unsigned)a_roff2[j] + uni2), 0, 0, 0);
+        }
+      }
+      if (!second) {
+#pragma unroll
+        for (int j = 0; j < LA; ++j) {
+          const int ih = a_ih0[j] + dy, iw = a_iw0[j] + dx;
+          const bool in = (unsigned)ih < (unsigned)a.Hi && (unsigned)iw < (unsigned)a.Wi;
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (CWT_LDS void*)(sb + (wv * LA + j) * 1024), 16,
+                                                   in ? a_roff[j] + uni : (int)0x80000000, 0, 0, 0);
+        }
       }
 #pragma unroll
       for (int j = 0; j < LB; ++j)

@@ -56,7 +56,13 @@ namespace cwt {
   X(128, 128, 12, 4, 1, 2, 16, 0) X(128, 128, 14, 4, 1, 2, 4, 0) X(128, 128, 15, 4, 1, 2, 2, 0) \
   X(128, 128, 16, 4, 1, 2, 6, 0) X(128, 128, 17, 4, 1, 2, 38, 0) X(128, 128, 18, 4, 1, 2, 64, 0) \
   /* ... and 256x256 var 3 without the A split */                                              \
-  X(256, 256, 13, 4, 2, 2, 16, 0)
+  X(256, 256, 13, 4, 2, 2, 16, 0)                                                              \
+  /* two A sources (PF bit 128, ConvSArgs::xs2: conv3 + downsample conv as one GEMM): var  */  \
+  /* kConvDualVar + v is var v's loop, on the tiles the fused shapes' plans take           */  \
+  X(128, 128, 24, 2, 2, 2, 128, 0) X(128, 128, 25, 4, 1, 2, 128, 0)                            \
+  X(128, 64, 25, 4, 1, 2, 128, 0) X(64, 128, 25, 4, 1, 2, 128, 0)
+
+constexpr int kConvDualVar = 20;
 
 struct ConvForm {
   int bm, bn, var, waves_m, waves_n, nstg, pf;

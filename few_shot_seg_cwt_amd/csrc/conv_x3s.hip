@@ -283,6 +283,19 @@ ConvPlan plan_conv_s(int prec, int M, int Co, int K, int batch) {
   }
 }
 
+// The x6 plan of a two-source 1x1 conv (the GEMM [M][K = Ci + Ci2] x [K][Co]): the shape's own plan
+// where its loop has a dual form, else 128x128 var 5 (Co % 128 == 0 for every conv3) on the same K split
+ConvPlan plan_conv_dual(int M, int Co, int K) {
+  ConvPlan p = plan_conv_s(6, M, Co, K);
+  const ConvForm* f = find_conv_form(6, p.bm, p.bn, p.var);
+  if (!f || !find_conv_form(6, p.bm, p.bn, f->var + kConvDualVar)) {
+    p.bm = 128;
+    p.bn = Co % 128 == 0 ? 128 : 64;
+    p.var = 5;
+  }
+  return p;
+}
+
 template <int PREC>
 static void launch_splitk_s(const ConvSArgs& a, int nsplit, hipStream_t st) {
   const long n = (long)a.M * (a.Co / 8);
@@ -298,13 +311,25 @@ static void launch_splitk_s(const ConvSArgs& a, int nsplit, hipStream_t st) {
 
 // prec 3: bf16x3 over S-layout operands; prec 1: plain bf16 (NHWC bf16 activations, weights in
 // 64-channel-block order)
-int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
-                    hipStream_t st, int prec) {
+static int launch_conv_s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
+                         hipStream_t st, int prec, bool reduce) {
   if (prec != 0 && prec != 1 && prec != 3 && prec != 6)
     return fail(CWT_EARG, "conv precision must be 3 (bf16x3), 1 (bf16), 0 (exact fp32) or 6 (bf16x6)");
   const ConvForm* form = find_conv_form(prec, p.bm, p.bn, p.var);
   if (!form) return fail(CWT_EARG, "no such conv form (conv_forms.h)");
   const bool batched = prec == 6 && a.batch > 1;
+  // two A sources: the plan names the loop (var v), the launch takes its dual form (kConvDualVar + v)
+  if ((form->pf & 128) != 0) return fail(CWT_EARG, "a dual conv form is named by its base form");
+  if (a.xs2) {
+    if (prec != 6 || batched || a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0)
+      return fail(CWT_EARG, "two-source conv: an x6 1x1 stride-1 conv only");
+    if (a.Ci2 <= 0 || a.Ci2 % 32 || a.K != a.Ci + a.Ci2 || a.kt_switch != a.Ci / 32 || a.stride2 < 1 ||
+        (a.Ho - 1) * a.stride2 >= a.Hi2 || (a.Wo - 1) * a.stride2 >= a.Wi2 ||
+        (long)a.N * a.Hi2 * a.Wi2 * a.Ci2 * 4 >= (1L << 31))
+      return fail(CWT_EARG, "two-source conv: bad second source");
+    form = find_conv_form(prec, p.bm, p.bn, form->var + kConvDualVar);
+    if (!form) return fail(CWT_EARG, "no dual form on this tile (conv_forms.h)");
+  }
   if ((prec == 0 || prec == 6) && (a.ys || a.res_s || (!a.y && !batched)))
     return fail(CWT_EARG, "fp32-operand conv: fp32 output and residual only");
   if (batched && (p.nsplit != 1 || !a.part || a.kh != 1 || a.kw != 1))
@@ -344,7 +369,7 @@ int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, s
   else
     launch(FamX3s{});
   CWT_LAUNCH_CHECK();
-  if (nsplit > 1 && !batched) {
+  if (nsplit > 1 && !batched && reduce) {
     main.part = part_ws;
     if (prec == 1)
       launch_splitk_s<1>(main, nsplit, st);
@@ -355,6 +380,37 @@ int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, s
     CWT_LAUNCH_CHECK();
   }
   return 0;
+}
+
+// The fp32 convs' split-K reduction alone, on caller partials [nsplit][M][Co] (the debug hooks)
+int launch_splitk_reduce_f32(const float* part, int nsplit, int M, int Co, const float* scale, const float* shift,
+                             int relu, float* y, hipStream_t st) {
+  if (!part || !scale || !shift || !y || nsplit < 1 || M < 1 || Co < 8 || Co % 8)
+    return fail(CWT_EARG, "split-K reduce: Co % 8, nsplit >= 1");
+  ConvSArgs a = {};
+  a.part = (float*)part;
+  a.M = M;
+  a.Co = Co;
+  a.scale = scale;
+  a.shift = shift;
+  a.relu = relu;
+  a.y = y;
+  a.y_ld = Co;
+  launch_splitk_s<0>(a, nsplit, st);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
+                    hipStream_t st, int prec) {
+  return launch_conv_s(a, p, stage, part_ws, part_ws_floats, st, prec, true);
+}
+
+int launch_conv_x3s_partials(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
+                             hipStream_t st, int prec) {
+  if (p.nsplit < 2 || a.batch > 1) return fail(CWT_EARG, "conv partials: a split-K plan of a single conv only");
+  if (a.res || a.res_s) return fail(CWT_EARG, "conv partials: the consumer's epilogue has no residual");
+  return launch_conv_s(a, p, stage, part_ws, part_ws_floats, st, prec, false);
 }
 
 }  // namespace cwt

@@ -197,12 +197,25 @@ struct ConvCall {
   int res_ld;
   int relu;
   bool out_f32;  // S-layout mode: this call writes fp32 (and takes an fp32 residual)
+  // x6: the second A source of a block's fused conv3 + downsample conv (L = Block::fused, Ci2 more
+  // input channels read from x2 [N][Hi2][Wi2][Ci2] at stride2; ConvSArgs::xs2), nullptr: a plain conv
+  const float* x2 = nullptr;
+  int Hi2 = 0, Wi2 = 0, Ci2 = 0, stride2 = 0;
+};
+
+// The input of a Winograd conv still in its producer's split-K partial planes (x = part
+// [nsplit][N*H*W][Ci]): the input transform sums them and applies the producer's BN and ReLU itself
+struct WinoSplitKSrc {
+  int nsplit;
+  const float *scale, *shift;
+  int relu;
 };
 
 ConvArgs make_args(const ConvCall& c);
 int force_conv_form(int prec, int bm, int bn, int Co, ConvPlan* p);
 int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int Ci, int Co, int d, int m, const __bf16* us,
                   const __bf16* ul, const float* scale, const float* shift, const float* res, int res_ld, int relu,
-                  float* y, int y_ld, int y_off, int stage, hipStream_t st, int bm = 0, int bn = 0);
+                  float* y, int y_ld, int y_off, int stage, hipStream_t st, int bm = 0, int bn = 0,
+                  const WinoSplitKSrc* sk = nullptr);
 
 }  // namespace cwt

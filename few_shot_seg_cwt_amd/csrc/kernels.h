@@ -45,6 +45,12 @@ struct ConvSArgs {
   // sums to part + b * M * Co (no epilogue); batch <= 1: off
   int batch;
   long xs_bstride, ws_bstride, wl_bstride;
+  // second A source of a 1x1 conv (x6 only, the dual forms of conv_forms.h: a bottleneck block's conv3
+  // and downsample conv as ONE GEMM over the concatenated K): K-tiles [0, kt_switch) read xs as usual,
+  // K-tiles [kt_switch, ktiles) read channel block kt - kt_switch of xs2, fp32 NHWC [N][Hi2][Wi2][Ci2],
+  // at pixel (oh * stride2, ow * stride2) of output pixel (oh, ow); xs2 == nullptr: off
+  const __bf16* xs2;
+  int Hi2, Wi2, Ci2, stride2, kt_switch;
 };
 
 // Conv weights are packed [Co][K] with K ordered (32-channel block, tap, channel in block):
@@ -122,6 +128,14 @@ int launch_splitk_epilogue(const ConvArgs& a, int nsplit, hipStream_t st);
 // The LDS-DMA convs (conv_x3s.hip; prec as launch_conv_x3s): the measured plan of the GEMM shape,
 // else the heuristic's.  batch: 0 a direct conv, else the Winograd form's GEMM count, M its tiles
 ConvPlan plan_conv_s(int prec, int M, int Co, int K, int batch = 0);
+// The x6 plan of a two-source 1x1 conv (ConvSArgs::xs2), K = Ci + Ci2: always one with a dual form
+ConvPlan plan_conv_dual(int M, int Co, int K);
+int launch_splitk_reduce_f32(const float* part, int nsplit, int M, int Co, const float* scale, const float* shift,
+                             int relu, float* y, hipStream_t st);
+// Folded weights of a block's conv3 + downsample conv as one GEMM: out [Co][K1 + K2] fp32, row co =
+// [s3[co] * W3[co][:] | sd[co] * Wd[co][:]], and shift_out = b3 + bd (bn_train.hip)
+int launch_fold_dual(const float* w3, const float* s3, const float* b3, int K1, const float* wd, const float* sd,
+                     const float* bd, int K2, int Co, float* out, float* shift_out, hipStream_t st);
 // Winograd F(2x2, 3x3) and F(4x4, 3x3) for the x6 path's stride-1 3x3 convs (wino.hip)
 struct WinoGeom {
   int N, H, W, d;  // image, dilation (= padding)
@@ -133,6 +147,8 @@ struct WinoGeom {
 WinoGeom wino_geom(int N, int H, int W, int d, int m = 2);
 int launch_wino_weights(const float* w_packed, int Co, int Ci, float* U, hipStream_t st, int m = 2);
 int launch_wino_in(const float* x, const WinoGeom& g, int Ci, float* V, hipStream_t st);
+int launch_wino_in_splitk(const float* part, int nsplit, const float* scale, const float* shift, int relu,
+                          const WinoGeom& g, int Ci, float* V, hipStream_t st);
 int launch_wino_out(const float* Mb, const WinoGeom& g, int Co, const float* scale, const float* shift, const float* res,
                     int res_ld, int relu, float* y, int y_ld, int y_off, hipStream_t st);
 // prec 3: bf16x3 (S-layout operands); prec 1: plain bf16 (NHWC bf16 activations, [Co][K]
@@ -141,6 +157,10 @@ int launch_wino_out(const float* Mb, const WinoGeom& g, int Co, const float* sca
 // NHWC activations and the fp32 packed weights
 int launch_conv_x3s(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
                     hipStream_t st, int prec = 3);
+// The same conv of a split-K plan (p.nsplit > 1) without its reduction: the raw partial planes
+// [nsplit][M][Co] stay in part_ws for a consumer that sums them itself (launch_wino_in_splitk)
+int launch_conv_x3s_partials(ConvSArgs a, const ConvPlan& p, int stage, float* part_ws, size_t part_ws_floats,
+                             hipStream_t st, int prec);
 int launch_split_act(const float* x, long P, int C, int ld, __bf16* out, hipStream_t st);
 int launch_split_w3(const float* w, long R, int K, __bf16* ws, __bf16* wl, hipStream_t st);
 int launch_occupy(int nwg, int us, hipStream_t st);  // timing study (cwt_debug_occupy)

@@ -147,10 +147,41 @@ __device__ __forceinline__ void wino_tile(long t, const WinoGeom& g, int& n, int
   n = (int)(r / g.d);
 }
 
+// One D element of the input transforms: 4 channels of an fp32 NHWC pixel, or (NS != 1) of the conv
+// that feeds this one, whose split-K partial planes [ns][M][C] are summed here in split order, then
+// fmaf(. , scale, shift) and ReLU -- conv_s_splitk_epilogue's operations in its order, so V is what
+// the epilogue kernel's stored map would have given.  NS: 1 the plain map, 0 a runtime ns, else ns.
+struct WinoSplitK {
+  const float *scale, *shift;  // [C] of the producing conv
+  long plane;                  // M * C floats between partial planes
+  int ns, relu;
+};
+template <int NS>
+__device__ __forceinline__ f32x4 wino_load(const float* __restrict__ p, const WinoSplitK& k, const f32x4& sc,
+                                           const f32x4& sh) {
+  f32x4 v = *(const f32x4*)p;
+  if constexpr (NS != 1) {
+    const int ns = NS > 0 ? NS : k.ns;
+#pragma unroll
+    for (int s = 1; s < (NS > 0 ? NS : 64); ++s) {
+      if (s >= ns) break;
+      v += *(const f32x4*)(p + s * k.plane);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = fmaf(v[i], sc[i], sh[i]);
+    if (k.relu) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
+    }
+  }
+  return v;
+}
+
 // V = B^T D B per tile and 4 channels; one thread per (tile, channel quad), consecutive threads
 // take consecutive channel quads (coalesced 16-B loads and stores)
+template <int NS>
 __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ x, WinoGeom g, int Ci,
-                                                      float* __restrict__ V) {
+                                                      float* __restrict__ V, WinoSplitK k) {
   const int q4 = Ci >> 2;
   const long idx = wino_xcd_index();
   if (idx >= g.T * q4) return;
@@ -158,6 +189,11 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ 
   const int c = (int)(idx - t * q4) * 4;
   int n, py, px, ti, tj;
   wino_tile(t, g, n, py, px, ti, tj);
+  f32x4 sc = {}, sh = {};
+  if constexpr (NS != 1) {
+    sc = *(const f32x4*)(k.scale + c);
+    sh = *(const f32x4*)(k.shift + c);
+  }
   f32x4 D[4][4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -166,7 +202,8 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ 
     for (int v = 0; v < 4; ++v) {
       const int ix = px + g.d * (2 * tj - 1 + v);
       const bool in = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-      D[u][v] = in ? *(const f32x4*)(x + (((long)n * g.H + iy) * g.W + ix) * Ci + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      D[u][v] = in ? wino_load<NS>(x + (((long)n * g.H + iy) * g.W + ix) * Ci + c, k, sc, sh)
+                   : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   f32x4 R[4][4];  // B^T D (rows)
@@ -189,7 +226,10 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ 
 
 // F(4x4,3x3) input transform of one 6-vector: B^T d, B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0;
 // 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
+// (no contraction into FMAs: which products the compiler fuses differed between the plain and the
+// split-K instantiation, and the two must give the same bits)
 __device__ __forceinline__ void wino4_bt(const f32x4 d[6], f32x4 r[6]) {
+#pragma clang fp contract(off)
   r[0] = 4.f * d[0] - 5.f * d[2] + d[4];
   r[1] = (d[3] + d[4]) - 4.f * (d[1] + d[2]);
   r[2] = (d[4] - d[3]) + 4.f * (d[1] - d[2]);
@@ -200,8 +240,9 @@ __device__ __forceinline__ void wino4_bt(const f32x4 d[6], f32x4 r[6]) {
 
 // V = B^T D B for F(4x4,3x3): one thread per (tile, channel quad) as wino_in_kernel; the 6x6
 // input tile column by column (B^T D), then each row of it (. B)
+template <int NS>
 __global__ __launch_bounds__(256) void wino4_in_kernel(const float* __restrict__ x, WinoGeom g, int Ci,
-                                                       float* __restrict__ V) {
+                                                       float* __restrict__ V, WinoSplitK k) {
   const int q4 = Ci >> 2;
   const long idx = wino_xcd_index();
   if (idx >= g.T * q4) return;
@@ -209,6 +250,11 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const float* __restrict__
   const int c = (int)(idx - t * q4) * 4;
   int n, py, px, ti, tj;
   wino_tile(t, g, n, py, px, ti, tj);
+  f32x4 sc = {}, sh = {};
+  if constexpr (NS != 1) {
+    sc = *(const f32x4*)(k.scale + c);
+    sh = *(const f32x4*)(k.shift + c);
+  }
   f32x4 R[6][6];  // B^T D: R[u][v]
 #pragma unroll
   for (int v = 0; v < 6; ++v) {
@@ -218,7 +264,8 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const float* __restrict__
     for (int u = 0; u < 6; ++u) {
       const int iy = py + g.d * (4 * ti - 1 + u);
       const bool in = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-      D[u] = in ? *(const f32x4*)(x + (((long)n * g.H + iy) * g.W + ix) * Ci + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      D[u] = in ? wino_load<NS>(x + (((long)n * g.H + iy) * g.W + ix) * Ci + c, k, sc, sh)
+                : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     f32x4 r[6];
     wino4_bt(D, r);
@@ -236,15 +283,35 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const float* __restrict__
   }
 }
 
-int launch_wino_in(const float* x, const WinoGeom& g, int Ci, float* V, hipStream_t st) {
-  if (Ci % 4) return fail(CWT_EARG, "wino_in: Ci % 4");
+template <int NS>
+static void launch_wino_in_ns(const float* x, const WinoGeom& g, int Ci, float* V, const WinoSplitK& k, hipStream_t st) {
   const long n = g.T * (Ci / 4);
   if (g.m == 4)
-    hipLaunchKernelGGL(wino4_in_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, g, Ci, V);
-  else if (g.m == 2)
-    hipLaunchKernelGGL(wino_in_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, g, Ci, V);
+    hipLaunchKernelGGL(wino4_in_kernel<NS>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, g, Ci, V, k);
   else
-    return fail(CWT_EARG, "winograd: output tile must be 2 or 4");
+    hipLaunchKernelGGL(wino_in_kernel<NS>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, x, g, Ci, V, k);
+}
+
+int launch_wino_in(const float* x, const WinoGeom& g, int Ci, float* V, hipStream_t st) {
+  if (Ci % 4) return fail(CWT_EARG, "wino_in: Ci % 4");
+  if (g.m != 2 && g.m != 4) return fail(CWT_EARG, "winograd: output tile must be 2 or 4");
+  launch_wino_in_ns<1>(x, g, Ci, V, WinoSplitK{}, st);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
+// The input transform of relu(fmaf(sum of the nsplit partial planes part[s][M][Ci], scale, shift)): the
+// split-K reduction and epilogue of the 1x1 conv that feeds this one, never stored (M = N * H * W)
+int launch_wino_in_splitk(const float* part, int nsplit, const float* scale, const float* shift, int relu,
+                          const WinoGeom& g, int Ci, float* V, hipStream_t st) {
+  if (Ci % 4) return fail(CWT_EARG, "wino_in: Ci % 4");
+  if (g.m != 2 && g.m != 4) return fail(CWT_EARG, "winograd: output tile must be 2 or 4");
+  if (!part || !scale || !shift || nsplit < 1 || nsplit > 64) return fail(CWT_EARG, "wino_in: bad split-K partials");
+  const WinoSplitK k{scale, shift, (long)g.N * g.H * g.W * Ci, nsplit, relu};
+  if (nsplit == 2)
+    launch_wino_in_ns<2>(part, g, Ci, V, k, st);
+  else
+    launch_wino_in_ns<0>(part, g, Ci, V, k, st);
   CWT_LAUNCH_CHECK();
   return 0;
 }

@@ -88,6 +88,29 @@ int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int 
                        const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
                        int nsplit, void* stream);
 
+/* The x6 extractor's fused conv3 + downsample conv of a bottleneck block, one launch:
+ * y [N*Ho*Wo][Co] = [relu]( t . (s3 W3)^T + x(stride2) . (sd Wd)^T + b3 + bd ), the rows folded on the
+ * device as cwt_backbone_load does (each product rounded once), then ONE 1x1 GEMM over K1 + K2 whose
+ * K-tiles past K1 / 32 read the second source.  t fp32 NHWC [N][Ho][Wo][K1]; x fp32 NHWC
+ * [N][Hi2][Wi2][K2], read at (oh, ow) * stride2; w3 [Co][K1], wd [Co][K2]; s3 b3 sd bd [Co].  bm / bn /
+ * nsplit as cwt_debug_conv_s: bm = 1000 * variant + rows names the loop (a base variant: 4 or 5), the
+ * launch takes its two-source form; a tile without one is CWT_EARG. */
+int cwt_debug_conv_x6_dual(cwt_ctx* ctx, const float* t, int N, int Ho, int Wo, int K1, const float* x, int Hi2,
+                           int Wi2, int K2, int stride2, const float* w3, const float* s3, const float* b3,
+                           const float* wd, const float* sd, const float* bd, int Co, int relu, float* y, int bm,
+                           int bn, int nsplit, void* stream);
+
+/* The Winograd input transform alone (wino.hip): V [(m+2)^2][T][C] of the fp32 NHWC map x [N][H][W][C]
+ * at dilation d, output tile m (2 or 4).  nsplit > 0: x holds the split-K partial planes
+ * [nsplit][N*H*W][C] of the map's producer instead, and the transform reads relu?(fmaf(sum of the
+ * planes, scale, shift)) -- the fused form the x6 extractor takes after a split-K conv1.
+ * cwt_debug_splitk_epilogue: the fp32 convs' split-K reduction kernel alone, y [M][Co] from part
+ * [nsplit][M][Co] (Co % 8 == 0). */
+int cwt_debug_wino_in(cwt_ctx* ctx, const float* x, int nsplit, const float* scale, const float* shift, int relu,
+                      int N, int H, int W, int C, int d, int m, float* V, void* stream);
+int cwt_debug_splitk_epilogue(cwt_ctx* ctx, const float* part, int nsplit, int M, int Co, const float* scale,
+                              const float* shift, int relu, float* y, void* stream);
+
 /* One CenterPivotConv4d layer + ReLU (src/model/conv4d.py:40-62) on the channels-last 4-D
  * tensor x [B][hA*wA][hB*wB][cin] -> y [B][hA*wA][hB*wB][cout]: Wa / Wb [cout][cin][3][3] the
  * a-plane / b-plane filters, ba / bb their biases.  variant 0: the library's kernel choice, 1:
