@@ -81,6 +81,11 @@ SIGNATURES = {
     "cwt_weight_average_train": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cwt_weight_average_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P]),
+    "cwt_weight_average_train_drop": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F,
+                                           C.c_uint64, _P]),
+    "cwt_weight_average_backward_drop": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P, _P, _P, _F, _F, C.c_uint64, _P]),
+    "cwt_seg_head_loss": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cwt_mmn_blend_backward": (_I, [_P, _P, _P, _I, _I64, _F, _P, _P, _P]),
     "cwt_linear_backward": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
     "cwt_deform_attn_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

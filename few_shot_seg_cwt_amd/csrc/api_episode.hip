@@ -326,9 +326,9 @@ int cwt_classify_scaled(cwt_ctx* ctx, const float* W, const float* f, const floa
 
 int cwt_classify(cwt_ctx* ctx, const float* W, const float* f, int B, int P, int C, float* logits, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(W && f && logits && C == 512 && B >= 1 && P >= 1, "bad arguments");
+  CWT_CHECK(W && f && logits && C >= 64 && C % 64 == 0 && C <= 2048 && B >= 1 && P >= 1, "bad arguments");
   CWT_HIP(hipSetDevice(ctx->device));
-  return launch_classify(W, f, B, P, logits, (hipStream_t)stream);
+  return launch_classify_c(W, 2L * C, f, B, P, C, logits, (hipStream_t)stream);
 }
 
 int cwt_classify_bwd(cwt_ctx* ctx, const float* dlogits, const float* f, int B, int P, int C, float* dW,
@@ -413,6 +413,34 @@ int cwt_seg_ce_fwd_bwd(cwt_ctx* ctx, const float* logits, const int64_t* target,
     return rc;
   return launch_seg_ce(logits, target, B, h, w, S, loss_out, dlogits, (uint8_t*)lbl, (AdaptScalars*)sc,
                        (double*)num, (hipStream_t)stream);
+}
+
+int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C,
+                      const int64_t* target, int S, int loss_type, float* loss_out, float* logits_out, float* d_f,
+                      void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(W && f && target && loss_out, "null buffer");
+  CWT_CHECK(C >= 64 && C % 64 == 0 && C <= 2048, "C must be a multiple of 64, at most 2048");
+  CWT_CHECK(B >= 1 && B <= 8, "need 1 <= B <= 8");
+  CWT_CHECK(h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) && S <= 32768, "need h, w, S >= 2");
+  CWT_CHECK(loss_type >= 0 && loss_type <= 2, "loss_type: 0 wt_ce, 1 wt_dc, 2 ce");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  float *lg, *sc;
+  double* part;
+  int rc;
+  if ((rc = ws(ctx, "shl.logits", (size_t)B * 2 * h * w, &lg)) ||
+      (rc = ws(ctx, "shl.part", seg_head_loss_part_doubles(B), &part)) ||
+      (rc = ws(ctx, "shl.sc", seg_head_loss_sc_floats(B), &sc)))
+    return rc;
+  if (logits_out) lg = logits_out;
+  // classifier 2 x 2*C per pixel (+ the same for d_f); per hi-res pixel two bilinear taps and a loss term, twice
+  Prof p(ctx, st, "seg_head_loss", (double)B * h * w * 4.0 * C * (d_f ? 2 : 1) + 40.0 * B * S * S * (d_f ? 2 : 1),
+         4.0 * B * h * w * C * (d_f ? 2 : 1) + 8.0 * B * S * S * (d_f ? 2 : 1));
+  if ((rc = launch_classify_c(W, 0, f, B, h * w, C, lg, st))) return rc;
+  rc = launch_seg_head_loss(W, lg, B, h, w, C, target, S, loss_type, loss_out, d_f, part, sc, st);
+  p.end();
+  return rc;
 }
 
 int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int64_t n, int num_classes,

@@ -523,13 +523,17 @@ int cwt_match_readout_backward(cwt_ctx* ctx, const float* corr2d, int B, int NA,
   return 0;
 }
 
+static bool wa_channels_ok(int C) { return (C >= 64 && C <= 512 && C % 64 == 0) || C == 1024 || C == 2048; }
+
 static int weight_average(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
                           const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
-                          const float* b_back, float* out, void* stream, float* tpg_keep, float* wavg_keep) {
+                          const float* b_back, float* out, void* stream, float* tpg_keep, float* wavg_keep,
+                          float p_att = 0.f, float p_proj = 0.f, unsigned long long seed = 0) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
   CWT_CHECK(x && w_tpg && b_theta && b_phi && b_g && w_back && b_back && out && N >= 1 && h >= 1 && w >= 1,
             "bad arguments");
-  CWT_CHECK(C == 512 || C == 1024 || C == 2048, "WeightAverage: c_in 512, 1024 or 2048");
+  CWT_CHECK(wa_channels_ok(C), "WeightAverage: c_in a multiple of 64 up to 512, or 1024 or 2048");
+  CWT_CHECK(p_att >= 0.f && p_att < 1.f && p_proj >= 0.f && p_proj < 1.f, "dropout probabilities must lie in [0, 1)");
   CWT_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const int co = C / 2;
@@ -549,12 +553,13 @@ static int weight_average(cwt_ctx* ctx, const float* x, int N, int h, int w, int
   } else if ((rc = launch_gemm_abt(x, w_tpg, 1, (int)P, 3 * co, C, tpg, st))) {
     return rc;
   }
-  if ((rc = launch_wa_attn(tpg, N, h, w, co, b_theta, b_phi, b_g, wavg, st))) return rc;
-  if (wa_f32d && gemm_f32d_ok((int)P, C, co, wavg, w_back, out, x)) {  // conv_back + bias + residual in one epilogue
+  if ((rc = launch_wa_attn(tpg, N, h, w, co, b_theta, b_phi, b_g, wavg, st, p_att, seed))) return rc;
+  // conv_back + bias + residual in one epilogue (not under proj_drop: the mask goes between them)
+  if (p_proj == 0.f && wa_f32d && gemm_f32d_ok((int)P, C, co, wavg, w_back, out, x)) {
     if ((rc = gemm_f32d(ctx, wavg, w_back, (int)P, C, co, out, b_back, x, C, st))) return rc;
   } else {
     if ((rc = launch_gemm_abt(wavg, w_back, 1, (int)P, C, co, back, st))) return rc;
-    if ((rc = launch_wa_residual(x, back, b_back, P * C, C, out, st))) return rc;
+    if ((rc = launch_wa_residual(x, back, b_back, P * C, C, out, st, p_proj, seed))) return rc;
   }
   p.end();
   return 0;
@@ -573,20 +578,41 @@ int cwt_weight_average_train(cwt_ctx* ctx, const float* x, int N, int h, int w, 
   return weight_average(ctx, x, N, h, w, C, w_tpg, b_theta, b_phi, b_g, w_back, b_back, out, stream, tpg, wavg);
 }
 
-int cwt_weight_average_backward(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
-                                const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
-                                const float* tpg, const float* wavg, const float* d_out, float* d_x,
-                                float* d_w_tpg, float* d_b_theta, float* d_b_phi, float* d_b_g, float* d_w_back,
-                                float* d_b_back, void* stream) {
+int cwt_weight_average_train_drop(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                  const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
+                                  const float* b_back, float* out, float* tpg, float* wavg, float p_att,
+                                  float p_proj, uint64_t seed, void* stream) {
+  if (!tpg || !wavg) return fail(CWT_EARG, "tpg / wavg is NULL");
+  return weight_average(ctx, x, N, h, w, C, w_tpg, b_theta, b_phi, b_g, w_back, b_back, out, stream, tpg, wavg, p_att,
+                        p_proj, (unsigned long long)seed);
+}
+
+// d_res: the gradient at the output (the residual's share of d_x); d_out: the gradient at
+// conv_back's output (d_res times the proj_drop mask, or d_res itself)
+static int weight_average_backward(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                   const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
+                                   const float* tpg, const float* wavg, const float* d_res, float* d_x,
+                                   float* d_w_tpg, float* d_b_theta, float* d_b_phi, float* d_b_g, float* d_w_back,
+                                   float* d_b_back, float p_att, float p_proj, unsigned long long seed,
+                                   void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(x && w_tpg && b_theta && b_phi && b_g && w_back && tpg && wavg && d_out && d_w_tpg && d_b_theta &&
+  CWT_CHECK(x && w_tpg && b_theta && b_phi && b_g && w_back && tpg && wavg && d_res && d_w_tpg && d_b_theta &&
                 d_b_phi && d_b_g && d_w_back && d_b_back && N >= 1 && h >= 1 && w >= 1,
             "bad arguments");
-  CWT_CHECK(C == 512 || C == 1024 || C == 2048, "WeightAverage: c_in 512, 1024 or 2048");
+  CWT_CHECK(wa_channels_ok(C), "WeightAverage: c_in a multiple of 64 up to 512, or 1024 or 2048");
+  CWT_CHECK(p_att >= 0.f && p_att < 1.f && p_proj >= 0.f && p_proj < 1.f, "dropout probabilities must lie in [0, 1)");
   CWT_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const int co = C / 2;
   const long P = (long)N * h * w, ldP = ld32(P);
+  const float* d_out = d_res;
+  if (p_proj > 0.f) {
+    float* dm;
+    int rc0;
+    if ((rc0 = ws(ctx, "wab.dmask", (size_t)P * C, &dm)) || (rc0 = launch_wa_proj_mask(d_res, P * C, p_proj, seed, dm, st)))
+      return rc0;
+    d_out = dm;
+  }
   float *wbt, *dwavg, *coef, *dtpg, *dot, *wvt, *dtt, *xt;
   int rc;
   if ((rc = ws(ctx, "wab.wbT", (size_t)co * C, &wbt)) || (rc = ws(ctx, "wab.dwavg", (size_t)P * co, &dwavg)) ||
@@ -599,7 +625,7 @@ int cwt_weight_average_backward(cwt_ctx* ctx, const float* x, int N, int h, int 
   if ((rc = launch_match_vt(w_back, 1, C, co, C, wbt, st)) || (rc = gemm_nt(ctx, d_out, wbt, (int)P, co, C, dwavg, st)))
     return rc;
   // softmax-weighted neighbourhood and the cosine similarities (msm_func.py:66-97)
-  if ((rc = launch_wa_bwd(tpg, N, h, w, co, b_theta, b_phi, b_g, dwavg, coef, dtpg, st))) return rc;
+  if ((rc = launch_wa_bwd(tpg, N, h, w, co, b_theta, b_phi, b_g, dwavg, coef, dtpg, st, p_att, seed))) return rc;
   // biases: column sums in a fixed order
   float* csw;
   const size_t csn = colsum_ws_floats(P, C);
@@ -621,15 +647,35 @@ int cwt_weight_average_backward(cwt_ctx* ctx, const float* x, int N, int h, int 
     float* wtt;
     if ((rc = ws(ctx, "wab.wtT", (size_t)C * 3 * co, &wtt))) return rc;
     if ((rc = launch_match_vt(w_tpg, 1, 3 * co, C, 3 * co, wtt, st))) return rc;
-    if (gemm_f32d_ok((int)P, C, 3 * co, dtpg, wtt, d_x, d_out)) {
-      if ((rc = gemm_f32d(ctx, dtpg, wtt, (int)P, C, 3 * co, d_x, nullptr, d_out, C, st))) return rc;
+    if (gemm_f32d_ok((int)P, C, 3 * co, dtpg, wtt, d_x, d_res)) {
+      if ((rc = gemm_f32d(ctx, dtpg, wtt, (int)P, C, 3 * co, d_x, nullptr, d_res, C, st))) return rc;
     } else if ((rc = gemm_nt(ctx, dtpg, wtt, (int)P, C, 3 * co, d_x, st)) ||
-               (rc = launch_add_inplace(d_x, d_out, P * C, st))) {
+               (rc = launch_add_inplace(d_x, d_res, P * C, st))) {
       return rc;
     }
   }
   p.end();
   return 0;
+}
+
+int cwt_weight_average_backward(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
+                                const float* tpg, const float* wavg, const float* d_out, float* d_x,
+                                float* d_w_tpg, float* d_b_theta, float* d_b_phi, float* d_b_g, float* d_w_back,
+                                float* d_b_back, void* stream) {
+  return weight_average_backward(ctx, x, N, h, w, C, w_tpg, b_theta, b_phi, b_g, w_back, tpg, wavg, d_out, d_x, d_w_tpg,
+                                 d_b_theta, d_b_phi, d_b_g, d_w_back, d_b_back, 0.f, 0.f, 0, stream);
+}
+
+int cwt_weight_average_backward_drop(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                     const float* b_theta, const float* b_phi, const float* b_g,
+                                     const float* w_back, const float* tpg, const float* wavg, const float* d_out,
+                                     float* d_x, float* d_w_tpg, float* d_b_theta, float* d_b_phi, float* d_b_g,
+                                     float* d_w_back, float* d_b_back, float p_att, float p_proj, uint64_t seed,
+                                     void* stream) {
+  return weight_average_backward(ctx, x, N, h, w, C, w_tpg, b_theta, b_phi, b_g, w_back, tpg, wavg, d_out, d_x, d_w_tpg,
+                                 d_b_theta, d_b_phi, d_b_g, d_w_back, d_b_back, p_att, p_proj, (unsigned long long)seed,
+                                 stream);
 }
 
 int cwt_mmn_blend_backward(cwt_ctx* ctx, const float* d_fq, const float* d_att_mean, int B, int64_t n, float att_wt,

@@ -147,7 +147,9 @@ __host__ __device__ static inline float align_corners_scale(int in_size, int out
 // (seed, stream, index) -> u in [0, 1) with 24 random bits; an element is kept iff u >= p and
 // then scaled by 1 / (1 - p), as nn.Dropout does.  The same function regenerates the mask in the
 // backward pass (nothing is stored) and in the tests (tests/dropout_ref.py restates it).
-// Streams: 1 = attention probabilities [B][2H][hw], 2 = fc output [2B][512].
+// Streams: 1 = attention probabilities [B][2H][hw], 2 = fc output [2B][512], 3 = Dropout2d over
+// (image, channel), 5 = the cycle mask [B][NB], 6 = WeightAverage's att_drop [N][h][w][9],
+// 7 = WeightAverage's proj_drop [N][h][w][C].
 __host__ __device__ __forceinline__ float dropout_uniform(unsigned long long seed, unsigned stream,
                                                          unsigned long long idx) {
   unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (idx + 1) + 0xD1B54A32D192ED03ull * (stream + 1);

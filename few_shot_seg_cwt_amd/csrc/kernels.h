@@ -262,7 +262,8 @@ int launch_token_norm(const float* x, long T, int C, float eps, float* xn, float
 int launch_token_norm_bwd(const float* xn, const float* nrm, const float* dxn, long T, int C, int ld_d, float eps,
                           int accum, float* dx, hipStream_t st);
 int launch_wa_bwd(const float* tpg, int N, int h, int w, int co, const float* bt, const float* bp, const float* bg,
-                  const float* dwavg, float* coef, float* dtpg, hipStream_t st);
+                  const float* dwavg, float* coef, float* dtpg, hipStream_t st, float p_att = 0.f,
+                  unsigned long long seed = 0);
 size_t colsum_ws_floats(long R, int Cc);
 int launch_colsum(const float* X, long R, int Cc, long ld, int accum, float* out, float* ws, size_t ws_floats,
                   hipStream_t st);
@@ -303,7 +304,12 @@ int launch_seg_ce(const float* logits, const int64_t* target, int B, int h, int 
 
 // ---- seg.hip ----
 int launch_normalize(const float* f, int B, int Pb, float* out, const float* W0, float* logits0, hipStream_t st);
-int launch_classify(const float* W, const float* f, int B, int Pb, float* logits, hipStream_t st);
+// W's batch stride wstride: 2 * 512 (a classifier per image), or 0 for one shared [2][512]
+int launch_classify(const float* W, const float* f, int B, int Pb, float* logits, hipStream_t st,
+                    long wstride = 2 * 512);
+// any C % 64 == 0 (C = 512 is launch_classify, bit for bit)
+int launch_classify_c(const float* W, long wstride, const float* f, int B, int Pb, int C, float* logits,
+                      hipStream_t st);
 int launch_classify_scaled(const float* W, const float* f, const float* inv, int B, int Pb, float* logits,
                            hipStream_t st);
 int launch_classify_bwd(const float* dl, const float* f, int B, int Pb, float* dW, hipStream_t st);
@@ -312,9 +318,16 @@ int launch_seg_metrics(const float* logits, const int64_t* target, int B, int h,
                        float* iut2 = nullptr);
 int launch_iou_preds(const int64_t* preds, const int64_t* target, long n, int K, int ignore, float* iut,
                      unsigned* counts_ws, hipStream_t st);
-// torch.optim.SGD step over a flat buffer
+// torch.optim.SGD step over a flat buffer (seg.hip)
 int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first,
                hipStream_t st);
+
+// ---- seg_loss.hip ----
+// part: [B][SHL_MAXBLK][6] doubles (per-block partial sums); sc: [B][4] + [4] floats
+size_t seg_head_loss_part_doubles(int B);
+size_t seg_head_loss_sc_floats(int B);
+int launch_seg_head_loss(const float* W, const float* logits, int B, int h, int w, int C, const int64_t* target, int S,
+                         int loss_type, float* loss_out, float* d_f, double* part, float* sc, hipStream_t st);
 
 // ---- cwt_attn.hip ----
 size_t attention_fold_floats(int C, int H);
@@ -381,8 +394,11 @@ int launch_match_masks(float* corr, int B, int NA, int NB, const uint8_t* ig, co
                        int* q2k, float* pv, int* pi, hipStream_t st, float drop_p = 0.f, unsigned long long seed = 0);
 int launch_match_zero_ig_cols(float* g, const uint8_t* ig, int B, int NA, int NB, hipStream_t st);
 int launch_wa_attn(const float* tpg, int N, int h, int w, int co, const float* bt, const float* bp, const float* bg,
-                   float* wavg, hipStream_t st);
-int launch_wa_residual(const float* x, const float* back, const float* b, long n, int C, float* out, hipStream_t st);
+                   float* wavg, hipStream_t st, float p_att = 0.f, unsigned long long seed = 0);
+// p_att / p_proj: WeightAverage's training-mode dropouts (streams 6 / 7 of dropout_scale)
+int launch_wa_residual(const float* x, const float* back, const float* b, long n, int C, float* out, hipStream_t st,
+                       float p_proj = 0.f, unsigned long long seed = 0);
+int launch_wa_proj_mask(const float* d_out, long n, float p_proj, unsigned long long seed, float* out, hipStream_t st);
 int launch_mmn_blend(const float* fq_in, const float* att, int B, long n, float att_wt, float* att_mean, float* fq_out,
                      hipStream_t st);
 

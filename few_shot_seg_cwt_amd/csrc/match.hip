@@ -1644,11 +1644,15 @@ int launch_match_zero_ig_cols(float* g, const uint8_t* ig, int B, int NA, int NB
 // tpg [N][P][3co]: theta | phi | g of every pixel (1x1 convs as one GEMM, biases not yet
 // added); per pixel: cos_r = CosineSimilarity(phi(x_r), theta(x)) over its 3x3 replicate-padded
 // neighbourhood r (torch: dot / (max(|phi|, 1e-8) max(|theta|, 1e-8))), softmax over the 9,
-// wavg = sum_r softmax_r g(x_r).  One workgroup per pixel, co / 256 channels per thread.
-template <int CPT>
+// wavg = sum_r softmax_r g(x_r).  One workgroup per pixel, co / 256 channels per thread (PART:
+// co < 256, the threads past co idle).  Training mode (msm_func.py:63,90): att_drop scales the
+// nine softmax weights by dropout_scale(p_att, seed, 6, pix 9 + r) before the average.
+#define WA_ON(k) (!PART || t + 256 * (k) < co)
+template <int CPT, bool PART = false>
 __global__ __launch_bounds__(256) void wa_attn_kernel(const float* __restrict__ tpg, int h, int w, int co,
                                                       const float* __restrict__ bt, const float* __restrict__ bp,
-                                                      const float* __restrict__ bg, float* __restrict__ wavg) {
+                                                      const float* __restrict__ bg, float* __restrict__ wavg,
+                                                      float p_att, unsigned long long seed) {
   const long P = (long)h * w;
   const long pix = blockIdx.x;  // n * P + p
   const long n = pix / P;
@@ -1660,7 +1664,7 @@ __global__ __launch_bounds__(256) void wa_attn_kernel(const float* __restrict__ 
   float th[CPT];
   const float* tp = tpg + pix * ld;
 #pragma unroll
-  for (int k = 0; k < CPT; ++k) th[k] = tp[t + 256 * k] + bt[t + 256 * k];
+  for (int k = 0; k < CPT; ++k) th[k] = WA_ON(k) ? tp[t + 256 * k] + bt[t + 256 * k] : 0.f;
   float part[19];
   part[18] = 0.f;
 #pragma unroll
@@ -1672,7 +1676,7 @@ __global__ __launch_bounds__(256) void wa_attn_kernel(const float* __restrict__ 
     float d = 0.f, nn = 0.f;
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
-      const float ph = q[t + 256 * k] + bp[t + 256 * k];
+      const float ph = WA_ON(k) ? q[t + 256 * k] + bp[t + 256 * k] : 0.f;
       d = fmaf(ph, th[k], d);
       nn = fmaf(ph, ph, nn);
     }
@@ -1704,6 +1708,10 @@ __global__ __launch_bounds__(256) void wa_attn_kernel(const float* __restrict__ 
     }
 #pragma unroll
     for (int r = 0; r < 9; ++r) sm[r] = cs[r] / se;
+    if (p_att > 0.f) {
+#pragma unroll
+      for (int r = 0; r < 9; ++r) sm[r] *= dropout_scale(p_att, seed, 6u, (unsigned long long)pix * 9 + r);
+    }
   }
   __syncthreads();
   float acc[CPT];
@@ -1715,17 +1723,36 @@ __global__ __launch_bounds__(256) void wa_attn_kernel(const float* __restrict__ 
     const float* q = tpg + (n * P + (long)yy * w + xx) * ld + 2 * co;
     const float a = sm[r];
 #pragma unroll
-    for (int k = 0; k < CPT; ++k) acc[k] = fmaf(a, q[t + 256 * k] + bg[t + 256 * k], acc[k]);
+    for (int k = 0; k < CPT; ++k)
+      if (WA_ON(k)) acc[k] = fmaf(a, q[t + 256 * k] + bg[t + 256 * k], acc[k]);
   }
 #pragma unroll
-  for (int k = 0; k < CPT; ++k) wavg[pix * co + t + 256 * k] = acc[k];
+  for (int k = 0; k < CPT; ++k)
+    if (WA_ON(k)) wavg[pix * co + t + 256 * k] = acc[k];
 }
+#undef WA_ON
 
 // out = x + (back + b): conv_back's bias and WeightAverage's residual (msm_func.py:99-104)
 __global__ void wa_residual_kernel(const float* __restrict__ x, const float* __restrict__ back,
                                    const float* __restrict__ b, long n, int C, float* __restrict__ out) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     out[i] = x[i] + (back[i] + b[i % C]);
+}
+
+// training mode (msm_func.py:64,100): proj_drop on conv_back's output (bias included) before the
+// residual add, element i of the NHWC map drawn as dropout_scale(p, seed, 7, i)
+__global__ void wa_residual_drop_kernel(const float* __restrict__ x, const float* __restrict__ back,
+                                        const float* __restrict__ b, long n, int C, float* __restrict__ out, float p,
+                                        unsigned long long seed) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    out[i] = x[i] + (back[i] + b[i % C]) * dropout_scale(p, seed, 7u, (unsigned long long)i);
+}
+
+// the backward's gradient at conv_back's output: out = d_out * the proj_drop mask
+__global__ void wa_proj_mask_kernel(const float* __restrict__ d_out, long n, float p, unsigned long long seed,
+                                    float* __restrict__ out) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    out[i] = d_out[i] * dropout_scale(p, seed, 7u, (unsigned long long)i);
 }
 
 // MMN.forward's tail (mmn.py:65-67): att_mean = mean over the B support rows of att_fq;
@@ -1742,19 +1769,34 @@ __global__ void mmn_blend_kernel(const float* __restrict__ fq_in, const float* _
 }
 
 int launch_wa_attn(const float* tpg, int N, int h, int w, int co, const float* bt, const float* bp, const float* bg,
-                   float* wavg, hipStream_t st) {
+                   float* wavg, hipStream_t st, float p_att, unsigned long long seed) {
   const dim3 grid((unsigned)((long)N * h * w));
-  if (co == 256) hipLaunchKernelGGL((wa_attn_kernel<1>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, wavg);
-  else if (co == 512) hipLaunchKernelGGL((wa_attn_kernel<2>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, wavg);
-  else if (co == 1024) hipLaunchKernelGGL((wa_attn_kernel<4>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, wavg);
-  else return fail(CWT_EARG, "WeightAverage: c_in / 2 must be 256, 512 or 1024");
+#define CWT_WA(...) \
+  hipLaunchKernelGGL((wa_attn_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, wavg, p_att, seed)
+  if (co == 256) CWT_WA(1);
+  else if (co == 512) CWT_WA(2);
+  else if (co == 1024) CWT_WA(4);
+  else if (co >= 32 && co < 256 && co % 32 == 0) CWT_WA(1, true);
+  else return fail(CWT_EARG, "WeightAverage: c_in / 2 must be a multiple of 32 up to 256, or 512 or 1024");
+#undef CWT_WA
   CWT_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_wa_residual(const float* x, const float* back, const float* b, long n, int C, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(wa_residual_kernel, dim3((unsigned)std::min<long>(65536, cdiv(n, 256))), dim3(256), 0, st, x,
-                     back, b, n, C, out);
+int launch_wa_residual(const float* x, const float* back, const float* b, long n, int C, float* out, hipStream_t st,
+                       float p_proj, unsigned long long seed) {
+  const dim3 grid((unsigned)std::min<long>(65536, cdiv(n, 256)));
+  if (p_proj > 0.f)
+    hipLaunchKernelGGL(wa_residual_drop_kernel, grid, dim3(256), 0, st, x, back, b, n, C, out, p_proj, seed);
+  else
+    hipLaunchKernelGGL(wa_residual_kernel, grid, dim3(256), 0, st, x, back, b, n, C, out);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_wa_proj_mask(const float* d_out, long n, float p_proj, unsigned long long seed, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(wa_proj_mask_kernel, dim3((unsigned)std::min<long>(65536, cdiv(n, 256))), dim3(256), 0, st, d_out,
+                     n, p_proj, seed, out);
   CWT_LAUNCH_CHECK();
   return 0;
 }

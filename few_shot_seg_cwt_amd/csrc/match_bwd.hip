@@ -513,12 +513,17 @@ int launch_token_norm_bwd(const float* xn, const float* nrm, const float* dxn, l
 // (the |.|^2 terms only where the norm exceeds the clamp).  wa_bwd_pix_kernel forms dtheta and
 // the per-(p, r) coefficients; wa_bwd_nbr_kernel gathers each pixel's dphi / dg from the pixels
 // whose neighbourhood holds it (at most the 3 x 3 around it), in a fixed order.
-template <int CPT>
+// With att_drop (wavg = sum_r m_r s_r g_r, m_r = dropout_scale(p_att, seed, 6, pix 9 + r) drawn
+// again here): ds_r = m_r dwavg . g_r, dg_r += m_r s_r dwavg; the softmax backward keeps the
+// pre-dropout s.  PART: co < 256, the threads past co idle.
+#define WA_ON(k) (!PART || t + 256 * (k) < co)
+template <int CPT, bool PART = false>
 __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict__ tpg, int h, int w, int co,
                                                          const float* __restrict__ bt, const float* __restrict__ bp,
                                                          const float* __restrict__ bg,
                                                          const float* __restrict__ dwavg, float* __restrict__ coef,
-                                                         float* __restrict__ dtpg) {
+                                                         float* __restrict__ dtpg, float p_att,
+                                                         unsigned long long seed) {
   const long P = (long)h * w;
   const long pix = blockIdx.x;
   const long n = pix / P;
@@ -531,8 +536,8 @@ __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict
   const float* tp = tpg + pix * ld;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
-    th[k] = tp[t + 256 * k] + bt[t + 256 * k];
-    dw[k] = dwavg[pix * co + t + 256 * k];
+    th[k] = WA_ON(k) ? tp[t + 256 * k] + bt[t + 256 * k] : 0.f;
+    dw[k] = WA_ON(k) ? dwavg[pix * co + t + 256 * k] : 0.f;
   }
   float part[28];
   part[18] = 0.f;
@@ -545,8 +550,8 @@ __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict
     float d = 0.f, nn = 0.f, dg = 0.f;
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
-      const float ph = q[co + t + 256 * k] + bp[t + 256 * k];
-      const float gv = q[2 * co + t + 256 * k] + bg[t + 256 * k];
+      const float ph = WA_ON(k) ? q[co + t + 256 * k] + bp[t + 256 * k] : 0.f;
+      const float gv = WA_ON(k) ? q[2 * co + t + 256 * k] + bg[t + 256 * k] : 0.f;
       d = fmaf(ph, th[k], d);
       nn = fmaf(ph, ph, nn);
       dg = fmaf(dw[k], gv, dg);
@@ -579,9 +584,11 @@ __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict
       sm[r] = expf(cs[r] - m);
       se += sm[r];
     }
-    float sds = 0.f;
+    float sds = 0.f, mk[9];
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
+      mk[r] = p_att > 0.f ? dropout_scale(p_att, seed, 6u, (unsigned long long)pix * 9 + r) : 1.f;
+      if (p_att > 0.f) tot[19 + r] *= mk[r];
       sm[r] = sm[r] / se;
       sds = fmaf(sm[r], tot[19 + r], sds);
     }
@@ -595,7 +602,7 @@ __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict
       cf[r] = ca;
       coef[pix * 27 + r] = ca;
       coef[pix * 27 + 9 + r] = cphi;
-      coef[pix * 27 + 18 + r] = sm[r];
+      coef[pix * 27 + 18 + r] = p_att > 0.f ? sm[r] * mk[r] : sm[r];
     }
     cf[9] = tn_raw > 1e-8f ? cth / tot[18] : 0.f;
   }
@@ -609,13 +616,15 @@ __global__ __launch_bounds__(256) void wa_bwd_pix_kernel(const float* __restrict
     const float* q = tpg + (n * P + (long)yy * w + xx) * ld + co;
     const float a = cf[r];
 #pragma unroll
-    for (int k = 0; k < CPT; ++k) dth[k] = fmaf(a, q[t + 256 * k] + bp[t + 256 * k], dth[k]);
+    for (int k = 0; k < CPT; ++k)
+      if (WA_ON(k)) dth[k] = fmaf(a, q[t + 256 * k] + bp[t + 256 * k], dth[k]);
   }
 #pragma unroll
-  for (int k = 0; k < CPT; ++k) dtpg[pix * ld + t + 256 * k] = dth[k];
+  for (int k = 0; k < CPT; ++k)
+    if (WA_ON(k)) dtpg[pix * ld + t + 256 * k] = dth[k];
 }
 
-template <int CPT>
+template <int CPT, bool PART = false>
 __global__ __launch_bounds__(256) void wa_bwd_nbr_kernel(const float* __restrict__ tpg, int h, int w, int co,
                                                          const float* __restrict__ bt, const float* __restrict__ bp,
                                                          const float* __restrict__ dwavg,
@@ -625,6 +634,7 @@ __global__ __launch_bounds__(256) void wa_bwd_nbr_kernel(const float* __restrict
   const long n = pix / P;
   const int q = (int)(pix - n * P), yq = q / w, xq = q - yq * w;
   const int t = threadIdx.x;
+  if (PART && t >= co) return;  // CPT = 1, no barrier below
   const long ld = 3L * co;
   float ph[CPT], dph[CPT], dg[CPT];
 #pragma unroll
@@ -661,13 +671,15 @@ __global__ __launch_bounds__(256) void wa_bwd_nbr_kernel(const float* __restrict
 }
 
 int launch_wa_bwd(const float* tpg, int N, int h, int w, int co, const float* bt, const float* bp, const float* bg,
-                  const float* dwavg, float* coef, float* dtpg, hipStream_t st) {
+                  const float* dwavg, float* coef, float* dtpg, hipStream_t st, float p_att,
+                  unsigned long long seed) {
   const dim3 grid((unsigned)((long)N * h * w));
-#define CWT_WAB(CPT)                                                                                              \
-  hipLaunchKernelGGL((wa_bwd_pix_kernel<CPT>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, dwavg, coef, dtpg); \
-  CWT_LAUNCH_CHECK();                                                                                             \
-  hipLaunchKernelGGL((wa_bwd_nbr_kernel<CPT>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, dwavg,                \
-                     (const float*)coef, dtpg);                                                                   \
+#define CWT_WAB(...)                                                                                               \
+  hipLaunchKernelGGL((wa_bwd_pix_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, bg, dwavg, coef, \
+                     dtpg, p_att, seed);                                                                           \
+  CWT_LAUNCH_CHECK();                                                                                              \
+  hipLaunchKernelGGL((wa_bwd_nbr_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, tpg, h, w, co, bt, bp, dwavg,         \
+                     (const float*)coef, dtpg);                                                                    \
   CWT_LAUNCH_CHECK();
   if (co == 256) {
     CWT_WAB(1)
@@ -675,10 +687,13 @@ int launch_wa_bwd(const float* tpg, int N, int h, int w, int co, const float* bt
     CWT_WAB(2)
   } else if (co == 1024) {
     CWT_WAB(4)
+  } else if (co >= 32 && co < 256 && co % 32 == 0) {
+    CWT_WAB(1, true)
   } else {
-    return fail(CWT_EARG, "WeightAverage backward: c_in / 2 must be 256, 512 or 1024");
+    return fail(CWT_EARG, "WeightAverage backward: c_in / 2 must be a multiple of 32 up to 256, or 512 or 1024");
   }
 #undef CWT_WAB
+#undef WA_ON
   return 0;
 }
 

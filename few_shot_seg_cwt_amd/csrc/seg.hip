@@ -56,7 +56,7 @@ int launch_normalize(const float* f, int B, int Pb, float* out, const float* W0,
 }
 
 __global__ __launch_bounds__(256) void classify_kernel(const float* __restrict__ W, const float* __restrict__ f,
-                                                       long P, int Pb, float* __restrict__ logits) {
+                                                       long P, int Pb, float* __restrict__ logits, long wstride) {
   constexpr int C = 512;
   const int lane = threadIdx.x & 63;
   const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void classify_kernel(const float* __restrict__
   const long pp = p - (long)b * Pb;
   const float* src = f + p * C + lane * 8;
   f32x4 u = *(const f32x4*)src, v = *(const f32x4*)(src + 4);
-  const float* w = W + (long)b * 2 * C + lane * 8;
+  const float* w = W + (long)b * wstride + lane * 8;
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -123,9 +123,44 @@ int launch_classify_scaled(const float* W, const float* f, const float* inv, int
   return 0;
 }
 
-int launch_classify(const float* W, const float* f, int B, int Pb, float* logits, hipStream_t st) {
+int launch_classify(const float* W, const float* f, int B, int Pb, float* logits, hipStream_t st, long wstride) {
   long P = (long)B * Pb;
-  hipLaunchKernelGGL(classify_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, W, f, P, Pb, logits);
+  hipLaunchKernelGGL(classify_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, W, f, P, Pb, logits, wstride);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
+// the classifier at any C % 64 == 0: one wave per pixel, lane owns channels lane, lane + 64, ...
+__global__ __launch_bounds__(256) void classify_c_kernel(const float* __restrict__ W, const float* __restrict__ f,
+                                                         long P, int Pb, int C, float* __restrict__ logits,
+                                                         long wstride) {
+  const int lane = threadIdx.x & 63;
+  const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= P) return;
+  const int b = (int)(p / Pb);
+  const long pp = p - (long)b * Pb;
+  const float* src = f + p * C;
+  const float* w = W + (long)b * wstride;
+  float s0 = 0.f, s1 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = src[c];
+    s0 = fmaf(w[c], v, s0);
+    s1 = fmaf(w[C + c], v, s1);
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (lane == 0) {
+    logits[(long)b * 2 * Pb + pp] = s0;
+    logits[(long)b * 2 * Pb + Pb + pp] = s1;
+  }
+}
+
+int launch_classify_c(const float* W, long wstride, const float* f, int B, int Pb, int C, float* logits,
+                      hipStream_t st) {
+  if (C == 512) return launch_classify(W, f, B, Pb, logits, st, wstride);
+  if (C < 64 || C % 64) return fail(CWT_EARG, "classify: C must be a multiple of 64");
+  long P = (long)B * Pb;
+  hipLaunchKernelGGL(classify_c_kernel, dim3(cdiv(P, 4)), dim3(256), 0, st, W, f, P, Pb, C, logits, wstride);
   CWT_LAUNCH_CHECK();
   return 0;
 }

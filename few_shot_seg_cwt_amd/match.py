@@ -524,10 +524,16 @@ class WeightAverage(torch.nn.Module):
         super().__init__()
         if R != 3:
             raise NotImplementedError("WeightAverage: R = 3 only")
+        drops = []
         for k in ("att_drop", "proj_drop"):
             p = (args.get(k, 0.0) if isinstance(args, dict) else getattr(args, k, 0.0)) if args is not None else 0.0
-            if p:
-                raise NotImplementedError("WeightAverage: att_drop / proj_drop are identities here (eval)")
+            p = float(p or 0.0)
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f"WeightAverage: {k} must lie in [0, 1), got {p}")
+            drops.append(p)
+        # msm_func.py:63-64: active under train() only; the seed of the last forward that drew masks
+        self.att_drop, self.proj_drop = drops
+        self.last_seed = None
         c_out = c_in // 2
         self.c_in, self.c_out, self.R = c_in, c_out, R
         self.conv_theta = torch.nn.Conv2d(c_in, c_out, 1, device=device)
@@ -554,6 +560,11 @@ class WeightAverage(torch.nn.Module):
         xt = as_tokens(x)
         ps = [self.conv_theta.weight, self.conv_theta.bias, self.conv_phi.weight, self.conv_phi.bias,
               self.conv_g.weight, self.conv_g.bias, self.conv_back.weight, self.conv_back.bias]
+        if self.training and (self.att_drop > 0.0 or self.proj_drop > 0.0):
+            # the reference's nn.Dropout on a device tensor never moves the host RNG stream (the W0
+            # draws): the seed comes from util.dropout_seed, one per forward
+            self.last_seed = dropout_seed()
+            return _WeightAverageDropFn.apply(xt, self.att_drop, self.proj_drop, self.last_seed, *ps)
         if _needs_grad(xt, *ps):
             return _WeightAverageFn.apply(xt, *ps)
         tpg, back = self._weights()
@@ -606,6 +617,53 @@ class _WeightAverageFn(torch.autograd.Function):
             "cwt_weight_average_backward")
         wshape = (co, Cc, 1, 1)
         return (dx, d_wtpg[:co].reshape(wshape), d_bt, d_wtpg[co:2 * co].reshape(wshape), d_bp,
+                d_wtpg[2 * co:].reshape(wshape), d_bg, d_wb.reshape(Cc, co, 1, 1), d_bb)
+
+
+class _WeightAverageDropFn(torch.autograd.Function):
+    """_WeightAverageFn with the training-mode dropouts (msm_func.py:63-64,90,100):
+    cwt_weight_average_train_drop / cwt_weight_average_backward_drop.  No mask is stored; the
+    backward draws both again from (att_drop, proj_drop, seed)."""
+
+    @staticmethod
+    def forward(ctx, xt, p_att, p_proj, seed, wt, bt, wp, bp, wg, bg, wb, bb):
+        N, Cc, h, w = xt.shape
+        co = Cc // 2
+        dev = xt.device
+        with torch.no_grad():
+            tpg_w = torch.cat([p.detach().reshape(co, Cc) for p in (wt, wp, wg)]).contiguous()
+            back = wb.detach().reshape(Cc, co).contiguous()
+        out = torch.empty((N, Cc, h, w), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
+        tpg = torch.empty((N * h * w, 3 * co), device=dev, dtype=torch.float32)
+        wavg = torch.empty((N * h * w, co), device=dev, dtype=torch.float32)
+        _lib.check(_lib.lib().cwt_weight_average_train_drop(
+            _lib.ctx(dev.index), _lib.ptr(xt), N, h, w, Cc, _lib.ptr(tpg_w), _lib.ptr(bt), _lib.ptr(bp), _lib.ptr(bg),
+            _lib.ptr(back), _lib.ptr(bb), _lib.ptr(out), _lib.ptr(tpg), _lib.ptr(wavg), float(p_att), float(p_proj),
+            int(seed), _lib.stream_ptr(dev)), "cwt_weight_average_train_drop")
+        ctx.save_for_backward(xt, tpg_w, bt, bp, bg, back, tpg, wavg)
+        ctx.drop = (float(p_att), float(p_proj), int(seed))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        xt, tpg_w, bt, bp, bg, back, tpg, wavg = ctx.saved_tensors
+        p_att, p_proj, seed = ctx.drop
+        N, Cc, h, w = xt.shape
+        co = Cc // 2
+        dev = xt.device
+        d = as_tokens(d_out)
+        dx = torch.empty_like(xt) if ctx.needs_input_grad[0] else None
+        f = dict(device=dev, dtype=torch.float32)
+        d_wtpg, d_bt, d_bp, d_bg = torch.empty((3 * co, Cc), **f), torch.empty(co, **f), torch.empty(co, **f), \
+            torch.empty(co, **f)
+        d_wb, d_bb = torch.empty((Cc, co), **f), torch.empty(Cc, **f)
+        _lib.check(_lib.lib().cwt_weight_average_backward_drop(
+            _lib.ctx(dev.index), _lib.ptr(xt), N, h, w, Cc, _lib.ptr(tpg_w), _lib.ptr(bt), _lib.ptr(bp), _lib.ptr(bg),
+            _lib.ptr(back), _lib.ptr(tpg), _lib.ptr(wavg), _lib.ptr(d), _lib.ptr(dx), _lib.ptr(d_wtpg), _lib.ptr(d_bt),
+            _lib.ptr(d_bp), _lib.ptr(d_bg), _lib.ptr(d_wb), _lib.ptr(d_bb), p_att, p_proj, seed,
+            _lib.stream_ptr(dev)), "cwt_weight_average_backward_drop")
+        wshape = (co, Cc, 1, 1)
+        return (dx, None, None, None, d_wtpg[:co].reshape(wshape), d_bt, d_wtpg[co:2 * co].reshape(wshape), d_bp,
                 d_wtpg[2 * co:].reshape(wshape), d_bg, d_wb.reshape(Cc, co, 1, 1), d_bb)
 
 

@@ -1,0 +1,97 @@
+"""The MMN / DeTr trainers' loss head on the device (cwt_seg_head_loss, csrc/seg_loss.hip):
+``criterion(F.interpolate(model.classifier(f), size=label, mode='bilinear', align_corners=True),
+label)`` of src/train_kshot.py:168-183 with ``criterion = SegLoss(loss_type)``
+(src/model/model_util.py:9-73) and the classifier of src/model/pspnet.py:183-187, as one call
+that also forms d loss / d f.  The S x S logits are never stored."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from .transformer import as_tokens
+
+WT_CE, WT_DC, CE = 0, 1, 2
+
+
+def loss_type_id(loss_type) -> int:
+    """SegLoss.forward's dispatch (model_util.py:16-24): 'wt_dc' / 'dc' -> dice, 'ce' -> the
+    unweighted CE, anything else -> the class-weighted CE."""
+    if isinstance(loss_type, int):
+        if loss_type not in (WT_CE, WT_DC, CE):
+            raise ValueError(f"loss_type id must be 0, 1 or 2, got {loss_type}")
+        return loss_type
+    if loss_type in ("wt_dc", "dc"):
+        return WT_DC
+    if loss_type == "ce":
+        return CE
+    return WT_CE
+
+
+def _call(W, ft, target, lt, want_logits, want_grad):
+    B, C, h, w = ft.shape
+    S = target.shape[-1]
+    dev = ft.device
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    logits = torch.empty((B, 2, h, w), device=dev, dtype=torch.float32) if want_logits else None
+    d_f = torch.empty_like(ft) if want_grad else None   # channels_last, as ft
+    _lib.check(_lib.lib().cwt_seg_head_loss(
+        _lib.ctx(dev.index), _lib.ptr(W), _lib.ptr(ft), B, h, w, C, _lib.ptr(target), S, lt, _lib.ptr(loss),
+        _lib.ptr(logits), _lib.ptr(d_f), _lib.stream_ptr(dev)), "cwt_seg_head_loss")
+    return loss, logits, d_f
+
+
+class _SegHeadLossFn(torch.autograd.Function):
+    """The loss and d loss / d f come out of the same call; backward scales the kept gradient."""
+
+    @staticmethod
+    def forward(ctx, ft, W, target, lt, want_logits):
+        loss, logits, d_f = _call(W, ft, target, lt, want_logits, True)
+        ctx.save_for_backward(d_f)
+        if logits is None:
+            logits = torch.empty(0, device=ft.device)
+        ctx.mark_non_differentiable(logits)
+        return loss.reshape(()), logits
+
+    @staticmethod
+    def backward(ctx, g, _g_logits):
+        (d_f,) = ctx.saved_tensors
+        return d_f * g, None, None, None, None
+
+
+def seg_head_loss(W: torch.Tensor, f: torch.Tensor, target: torch.Tensor, loss_type="wt_dc",
+                  return_logits: bool = False):
+    """W [2, C] (or [1, 2, C] / [2, C, 1, 1]: the binary classifier's weight, a constant), f
+    [B, C, h, w] features, target int64 [B, S, S] (255 = ignore) -> the scalar loss, with autograd
+    to f; with return_logits also the low-resolution logits [B, 2, h, w] (for the IoU logging)."""
+    _lib.require(f, "f")
+    _lib.require(W, "W")
+    _lib.require(target, "target", torch.int64)
+    if f.dim() != 4 or target.dim() != 3 or target.shape[0] != f.shape[0] or target.shape[1] != target.shape[2]:
+        raise ValueError(f"f must be [B,C,h,w] and target [B,S,S], got {tuple(f.shape)} and {tuple(target.shape)}")
+    C = f.shape[1]
+    if W.numel() != 2 * C:
+        raise ValueError(f"W must hold 2 x {C} weights, got {tuple(W.shape)}")
+    W = W.detach().reshape(2, C).contiguous()
+    target = target.contiguous()
+    lt = loss_type_id(loss_type)
+    ft = as_tokens(f)
+    if torch.is_grad_enabled() and f.requires_grad:
+        loss, logits = _SegHeadLossFn.apply(ft, W, target, lt, bool(return_logits))
+    else:
+        loss, logits, _ = _call(W, ft.detach(), target, lt, return_logits, False)
+        loss = loss.reshape(())
+    return (loss, logits) if return_logits else loss
+
+
+class SegLoss(torch.nn.Module):
+    """model_util.py:9-24 by name ('wt_dc', 'dc', 'ce', anything else -> 'wt_ce'), applied to
+    features through the classifier weight: ``SegLoss(t)(W, f, target)``."""
+
+    def __init__(self, loss_type: str = "wt_ce", num_cls: int = 2, fg_idx: int = 1):
+        super().__init__()
+        if num_cls != 2 or fg_idx != 1:
+            raise NotImplementedError("SegLoss: 2-way episodes with foreground index 1 only")
+        self.loss_type = loss_type
+
+    def forward(self, W, f, target, return_logits: bool = False):
+        return seg_head_loss(W, f, target, self.loss_type, return_logits)

@@ -260,7 +260,8 @@ int cwt_classify_scaled(cwt_ctx* ctx, const float* W, const float* f, const floa
                         float* logits, void* stream);
 
 /* Per-pixel classifier logits = W . f (test.py:200-204 Pseudo_cls; train.py:259-261 matmul).
- * W: device [B,2,C]; f: NHWC [B,P,C]; logits: device [B,2,P] (NCHW [B,2,h,w]). */
+ * W: device [B,2,C]; f: NHWC [B,P,C]; logits: device [B,2,P] (NCHW [B,2,h,w]).
+ * C a multiple of 64, at most 2048. */
 int cwt_classify(cwt_ctx* ctx, const float* W, const float* f, int B, int P, int C, float* logits,
                  void* stream);
 
@@ -331,6 +332,24 @@ int cwt_seg_metrics_pair(cwt_ctx* ctx, const float* logits, const float* logits0
  */
 int cwt_seg_ce_fwd_bwd(cwt_ctx* ctx, const float* logits, const int64_t* target, int B, int h,
                        int w, int S, float* loss_out, float* dlogits, void* stream);
+
+/*
+ * The MMN / DeTr trainers' loss head in one call (src/train_kshot.py:168-183): the per-pixel
+ * classifier logits = W . f (src/model/pspnet.py:183-187, as cwt_classify), the bilinear
+ * align_corners=True upsample to the S x S label, SegLoss (src/model/model_util.py:9-73) and the
+ * gradient of the loss w.r.t. the feature map f.  W is a constant (the trainer never optimises it).
+ * loss_type 0 'wt_ce': CrossEntropyLoss(weight [1, #bg/#fg], ignore_index 255), the counts over
+ *   the whole target; 2 'ce': the same, unweighted; 1 'wt_dc' (= 'dc'): weighted_dice_loss,
+ *   p = sigmoid(z), t_k = [label == k], loss = sum_{b,k} (1 - 2 sum(t p) / max(sum(p^2) + sum(t),
+ *   1e-8)) / B (pixels labelled 255 have t = 0 in both channels and still count in sum(p^2)).
+ * W device [2][C]; f device NHWC [B][h][w][C]; target device int64 [B][S][S]; loss_out device
+ * fp32 [1]; logits_out device [B][2][h][w] or NULL; d_f device [B][h][w][C] or NULL (overwritten).
+ * C a multiple of 64, at most 2048; 1 <= B <= 8; h, w, S >= 2 (any ratio).  Every sum runs in a
+ * fixed order (no float atomics): two calls on the same inputs give the same bits.  No host sync.
+ */
+int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C,
+                      const int64_t* target, int S, int loss_type, float* loss_out, float* logits_out,
+                      float* d_f, void* stream);
 
 /* intersectionAndUnionGPU on argmax maps (util.py:280-308): preds/target device int64 [n];
  * preds[target==ignore] are ignored; histc over classes 0..num_classes-1 (num_classes <= 16).
@@ -508,6 +527,27 @@ int cwt_corr_backward(cwt_ctx* ctx, const float* q, const float* k, int B, int P
 int cwt_weight_average_train(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
                              const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
                              const float* b_back, float* out, float* tpg, float* wavg, void* stream);
+
+/* cwt_weight_average_train with WeightAverage's training-mode dropouts (msm_func.py:63-64,90,100):
+ * att_drop on the nine softmax weights of every pixel (draw index ((n h + y) w + x) 9 + r, stream 6
+ * of the counter-based generator) and proj_drop element-wise on conv_back's output before the
+ * residual add (draw index = the NHWC linear index, stream 7).  Nothing is stored: the backward
+ * regenerates both masks from (p_att, p_proj, seed).  wavg is the post-dropout average.  With both
+ * probabilities 0 this is cwt_weight_average_train.  Here C / 2 may also be a multiple of 32
+ * below 256. */
+int cwt_weight_average_train_drop(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                  const float* b_theta, const float* b_phi, const float* b_g, const float* w_back,
+                                  const float* b_back, float* out, float* tpg, float* wavg, float p_att,
+                                  float p_proj, uint64_t seed, void* stream);
+
+/* cwt_weight_average_backward for a forward by cwt_weight_average_train_drop with the same
+ * (p_att, p_proj, seed); the softmax backward uses the pre-dropout softmax. */
+int cwt_weight_average_backward_drop(cwt_ctx* ctx, const float* x, int N, int h, int w, int C, const float* w_tpg,
+                                     const float* b_theta, const float* b_phi, const float* b_g,
+                                     const float* w_back, const float* tpg, const float* wavg, const float* d_out,
+                                     float* d_x, float* d_w_tpg, float* d_b_theta, float* d_b_phi, float* d_b_g,
+                                     float* d_w_back, float* d_b_back, float p_att, float p_proj, uint64_t seed,
+                                     void* stream);
 
 /* WeightAverage's backward (msm_func.py:66-104): d_out device [N][h][w][C] -> d_x device
  * [N][h][w][C] (or NULL), d_w_tpg device [3 C/2][C], d_b_theta / d_b_phi / d_b_g [C/2], d_w_back
