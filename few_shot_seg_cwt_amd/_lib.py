@@ -132,6 +132,8 @@ SIGNATURES = {
     "cwt_debug_splitk_epilogue": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "cwt_debug_conv_form": (_I, [_I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_conv_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "cwt_debug_adapt_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "cwt_debug_adapt_form": (_I, [_I, C.POINTER(_I)]),
     "cwt_debug_census": (_I, [_P, _I, _P, _P]),
     "cwt_debug_tail_stamps": (_I, [_P, _P, _I64, _P]),
     "cwt_debug_occupy": (_I, [_P, _I, _I, _P]),

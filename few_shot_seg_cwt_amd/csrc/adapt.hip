@@ -667,14 +667,12 @@ static int enqueue_adapt_steps(const AdaptDevArgs* dargs, const float* f_ws, con
 // ---------------------------------------------------------------------------------------
 constexpr int PA_T = 1024;
 constexpr int PA_NW = 16;
-constexpr int PA_UC = 31;            // max lo-res columns owned per unit (a.uc: 31, or 15 when that fits the CUs)
+// (PA_UC, PA_R_DEFAULT, PA_EW: adapt_plan.h)
 constexpr int PA_NC = PA_UC + 1;     // storage stride of a unit's lo-res row (held columns: a.uc + 1)
 constexpr int PA_NPX = 2 * PA_NC;    // lo-res pixels per unit: one per lane
 constexpr int PA_CPW = 512 / PA_NW;  // channels per wave
 constexpr int PA_R = 16;             // max replica rows of dW[1] (and arrival counters) per slot
-constexpr int PA_R_DEFAULT = 8;      // rows used (CWT_ADAPT_PR: 2, 4, 8 or 16)
 constexpr int PA_NSLOT = 4;          // accumulator slots (step s adds into s % 4)
-constexpr int PA_EW = 4;             // episodes one workgroup's units may span
 constexpr bool PA_HIRES2 = true;     // the lockstep pair's hi-res passes interleaved (hires_pass2)
 #ifndef PA_CNT_STRIDE_WORDS
 #define PA_CNT_STRIDE_WORDS 32
@@ -893,12 +891,9 @@ struct PaScrAlias {
 // s_memtime at 8 points of every step, realtime at its arrival ([8]) and when its poll matched
 // ([9]) into stamps[step][g][10], and realtime/memtime at entry and exit into
 // stamps[iters][g][0..3] (tools/persist_stamps.py).
-// NRES 1: one unit per workgroup, its f in registers; 2: up to two units per workgroup, the
-// first in registers, the second in LDS (128 KB, lane-major: conflict-free); 4: up to three
-// units in lockstep, the first and third in registers, the second in LDS; 3: units streamed
-// every step, each wave's slice by LDS-DMA into its private 8 KB while the previous unit is
-// computed; 0: units streamed from L2 into registers (opt-in, slower).  Fewer workgroups make each step's barrier cheaper and leave CUs to the
-// next episode's extractor pass (EpisodePipeline).
+// NRES: the form (AdaptForm, adapt_plan.h, where each is described); its traits come from
+// pa_form_traits.  Fewer workgroups make each step's barrier cheaper and leave CUs to the next
+// episode's extractor pass (EpisodePipeline).
 // MODE only separates instantiations so that rocprofv3's per-kernel statistics attribute each
 // launch to the leg that made it: 0 the product kernel (every timed launch); 1 STAMPS (above);
 // 2 FLOOR, the latency-floor study (CWT_ADAPT_DBG & 64: every unit's arithmetic and atomics
@@ -911,23 +906,17 @@ __device__ __forceinline__ bool adapt_persist_body(const PersistArgs& a, unsigne
   constexpr bool STAMPS = MODE == 1;
   constexpr bool FLOOR = MODE == 2;
   constexpr int C = 512;
-  constexpr int EWK = (NRES >= 2) ? 2 : NRES == 1 ? 1 : PA_EW;  // episodes a workgroup's units may span
-  constexpr bool LOCK = NRES == 2 || NRES == 4;  // units in lockstep, the second one's f in fl2
-  // NRES 5: two units in lockstep, both in registers (the second one in cur2, as NRES 4's third):
-  // no LDS reads of f in the z and dW passes
-  constexpr bool BREG = NRES == 5;
-  // NRES 6: NRES 3 with the workgroup's first unit resident in registers (res): its f is never
-  // streamed, the DMA ring carries only the units after it (5-shot 641^2: 4-5 units per workgroup,
-  // about a fifth of the per-step stream)
-  constexpr bool STREAM = NRES == 3 || NRES == 6;
-  constexpr bool RES1 = NRES == 6;
+  constexpr PaFormTraits FT = pa_form_traits(NRES);
+  constexpr int EWK = FT.ewk;        // episodes a workgroup's units may span
+  constexpr bool LOCK = FT.lock;     // units in lockstep, the second one's f in fl2
+  constexpr bool BREG = FT.breg;     // the pair's second unit in registers (cur2, as PA_LOCK3's third)
+  constexpr bool STREAM = FT.stream;
+  constexpr bool RES1 = FT.res1;     // the first unit resident in registers (res)
   __shared__ float fl2[LOCK ? PA_NW : 1][PA_CPW][LOCK ? 64 : 1];
-  __shared__ __attribute__((aligned(16))) float fs3[(NRES == 3 || NRES == 6) ? PA_NW * 64 * PA_CPW : 4];  // NRES 3, 6: per-wave f slices
+  __shared__ __attribute__((aligned(16))) float fs3[STREAM ? PA_NW * 64 * PA_CPW : 4];  // per-wave f slices
   __shared__ float dlw[PA_NW][EWK][PA_CPW];     // d = W1 - W0 of each wave's channels (wave-private)
   __shared__ float wlw[PA_NW][EWK][2][PA_CPW];  // W0, W1 of each wave's channels (wave-private)
-  // NRES 2 runs its two units in lockstep (one set of LDS barriers, one butterfly and one set
-  // of atomics per step when both units belong to one episode): the second unit's copies [1]
-  constexpr int NU = (NRES == 2 || NRES == 5) ? 2 : NRES == 4 ? 3 : 1;
+  constexpr int NU = FT.nu;  // units in lockstep: the later units' copies [1], [2]
   __shared__ std::conditional_t<NRES == 4, PaScrAlias<NU>, PaScrSep<NU>> scr;
   auto& zpart_u = scr.zpart;
   auto& P0_u = scr.P0;
@@ -947,7 +936,7 @@ __device__ __forceinline__ bool adapt_persist_body(const PersistArgs& a, unsigne
   const int u0 = (int)(((long)g * a.units) / G), u1 = (int)(((long)(g + 1) * a.units) / G);
   const int per_ep = a.nshot * a.ntile;
   const int e_lo = u0 / per_ep, e_hi = (u1 - 1) / per_ep;
-  const int new_ = e_hi - e_lo + 1;  // episodes spanned (<= PA_EW, checked on the host)
+  const int new_ = e_hi - e_lo + 1;  // episodes spanned (<= EWK: adapt_plan)
   const int nrep = a.nrep;
   const int rep = g % nrep;
   unsigned* err = a.cnt + PA_R * PA_CNT_STRIDE;
@@ -1643,118 +1632,44 @@ __global__ __launch_bounds__(PA_T) void adapt_persist_tail_kernel(PersistArgs a,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Host side of the persistent loop: G = min(units, CUs).  Returns 1 (not an error) when the
-// geometry does not fit it (the caller then uses the per-step launches).
-static int g_cu_count = 0;
-static int persist_geometry(int E, int n, int h, int w, int upw_pref, int* G_out, int* units_out, int* ncb_out,
-                            int* nres_out, int* uc_out) {
-  if (!g_cu_count) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&g_cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      g_cu_count = 0;
-    if (g_cu_count <= 0) return 1;
-  }
-  // 31 owned columns: 15 halves each workgroup's hi-res pixels but doubles the workgroups, and
-  // the barrier's atomics and arrivals cost more than that saves (1-shot 473: 7.0 vs 5.9 us per
-  // step, tools/persist_stamps.py); CWT_ADAPT_UC=15 selects it
-  int uc = PA_UC;
-  const char* ucs = getenv("CWT_ADAPT_UC");
-  if (ucs && (atoi(ucs) == 15 || atoi(ucs) == 31)) uc = atoi(ucs);
-  const int ncb = cdiv(w - 1, uc);
-  const int ntile = (h - 1) * ncb;
-  const long units = (long)E * n * ntile;
-  // units per workgroup: 1 (f in registers) or 2 (the second unit's f in LDS): half the
-  // workgroups and CUs left for a concurrent extractor pass.  The context's choice
-  // (cwt_ctx_set_adapt_units: EpisodePipeline asks for 2), else CWT_ADAPT_UPW, else 1 while
-  // that takes at most half the CUs (1-shot 473^2: 118 workgroups) and 2 beyond
-  const char* upws = getenv("CWT_ADAPT_UPW");
-  const int upw = upw_pref ? upw_pref : upws ? (atoi(upws) == 1 ? 1 : 2) : (units <= g_cu_count / 2 ? 1 : 2);
-  int G = (int)std::min<long>((units + upw - 1) / upw, g_cu_count);
-  const long k = (units + G - 1) / G;  // units per workgroup (max)
-  const long per_ep = (long)n * ntile;
-  const long span = (k - 1 + per_ep - 1) / per_ep + 1;  // episodes a workgroup's range can touch
-  // k >= 4 (5-shot 641^2: 1200 units, 4-5 per workgroup): units streamed per wave through LDS
-  // (nres 3), 6.04 against 6.35 ms for the step launches; at k = 3 (5-shot 473^2) the stream is
-  // slower than the step launches (4.09 against 3.53 ms: the 37 MB per step of f come from the
-  // Infinity Cache and the 3-unit workgroups set the pace), so those keep the step launches.
-  // CWT_ADAPT_STREAM=0 disables it, =1 allows it from k = 3.
-  const char* sts = getenv("CWT_ADAPT_STREAM");
-  const int stream_from = sts ? (sts[0] == '0' ? 1 << 30 : 3) : 4;
-  // k = 3 (5-shot 473^2: 590 units on 197 workgroups): three units in lockstep, two in
-  // registers and one in LDS (nres 4); CWT_ADAPT_LOCK3=0 returns it to the step launches
-  const char* l3s = getenv("CWT_ADAPT_LOCK3");
-  const bool lock3 = !(l3s && l3s[0] == '0');
-  // k = 2: both units in registers (nres 5) unless CWT_ADAPT_BREG=0 (the second unit's f in LDS, nres 2)
-  const char* brs = getenv("CWT_ADAPT_BREG");
-  const bool breg = !(brs && brs[0] == '0');
-  int nres = k == 1 ? 1 : (k == 2 && span <= 2) ? (breg ? 5 : 2) : (k == 3 && span <= 2 && lock3) ? 4 : 0;
-  if (nres == 0 && k >= stream_from && span <= 2) nres = 3;
-  // the streamed form with the first unit resident in registers (nres 6): opt in with
-  // CWT_ADAPT_RES1=1 -- measured slower (5-shot 641^2 alone: 6.77 against 5.87 ms; the resident f
-  // does not fit beside the streamed unit at 1,024 threads and 25 VGPRs spill to scratch, whose
-  // per-step reloads cost more than the fifth of the stream they save; profiles/r4/run_n)
-  const char* r1s = getenv("CWT_ADAPT_RES1");
-  if (nres == 3 && r1s && r1s[0] == '1') nres = 6;
-  if (span > (nres >= 2 ? 2 : PA_EW)) return 1;
-  // three units per workgroup: as few workgroups as that takes (5-shot 473^2: 197, not 256 with
-  // two or three units each -- the step waits for the three-unit ones either way, and fewer
-  // workgroups make the barrier cheaper and leave CUs free)
-  if (nres == 4) G = (int)((units + 2) / 3);
-  *G_out = G;
-  *units_out = (int)units;
-  *ncb_out = ncb;
-  *uc_out = uc;
-  *nres_out = nres;
-  // the register-streamed form (nres 0) is not faster than the step launches: opt in only
-  const char* pe = getenv("CWT_ADAPT_PERSIST");
-  if (!*nres_out && !(pe && pe[0] == '2')) return 1;
-  return 0;
-}
-
-static int enqueue_adapt_persist(const float* f, const uint8_t* lbl_ws, const AdaptScalars* sc, float* acc3,
-                                 unsigned* cnt, const AdaptDevArgs* dargs, int E, int n, int h, int w, int S,
-                                 int iters, int G, int units, int ncb, int nres, int uc, unsigned* status,
-                                 long spin_limit, hipStream_t st, const FusedTail* tail) {
+// Host side of the persistent loop: the launch of a plan (adapt_plan.h) that names a persistent form.
+static int enqueue_adapt_persist(const AdaptPlan& p, const float* f, const AdaptWs& ws, unsigned* cnt, int S,
+                                 unsigned* status, long spin_limit, hipStream_t st, const FusedTail* tail) {
   PersistArgs a;
   a.status = status;
   a.spin_limit = spin_limit > 0 ? spin_limit : PA_SPIN_LIMIT;
   a.f = f;
-  a.lbl = lbl_ws;
-  a.sc = sc;
-  a.dargs = dargs;
-  a.acc = acc3;
+  a.lbl = ws.lbl;
+  a.sc = ws.sc;
+  a.dargs = ws.dargs;
+  a.acc = ws.acc;
   a.cnt = cnt;
-  a.h = h;
-  a.w = w;
+  a.h = p.h;
+  a.w = p.w;
   a.S = S;
-  a.nshot = n;
-  a.nep = E;
+  a.nshot = p.n;
+  a.nep = p.E;
 
-  a.iters = iters;
-  a.ncb = ncb;
-  a.ntile = (h - 1) * ncb;
-  a.units = units;
-  a.G = G;
-  a.uc = uc;
-  const char* pr = getenv("CWT_ADAPT_PR");
-  a.nrep = pr ? atoi(pr) : PA_R_DEFAULT;
-  if (a.nrep != 2 && a.nrep != 4 && a.nrep != 8 && a.nrep != 16) a.nrep = PA_R_DEFAULT;
-  const char* dbg = getenv("CWT_ADAPT_DBG");
-  const int dbgv = dbg ? atoi(dbg) : 0;
-  // MODE: 1 stamps (timing study), 2 latency floor (& 64), 3 side leg (& 128), 0 product
-  const int mode = (dbgv & 32) ? 1 : (dbgv & 64) ? 2 : (dbgv & 128) ? 3 : 0;
+  a.iters = p.iters;
+  a.ncb = p.ncb;
+  a.ntile = (p.h - 1) * p.ncb;
+  a.units = p.units;
+  a.G = p.G;
+  a.uc = p.uc;
+  a.nrep = p.nrep;
+  const int G = p.G, mode = p.mode;
   if (tail) {  // the fused tail: the product instantiation of the two-unit register form only
-    if (nres != 5 || mode != 0 || E != 1 || !tail->args || !tail->wq)
+    if (p.form != PA_PAIR_REG || mode != 0 || p.E != 1 || !tail->args || !tail->wq)
       return fail(CWT_EARG, "fused tail: needs the two-unit persistent loop (nres 5), one episode, product mode");
     a.wq = tail->wq;
-    hipLaunchKernelGGL((adapt_persist_tail_kernel<5>), dim3(G), dim3(PA_T), 0, st, a, *tail->args, tail->stamps);
+    hipLaunchKernelGGL((adapt_persist_tail_kernel<PA_PAIR_REG>), dim3(G), dim3(PA_T), 0, st, a, *tail->args,
+                       tail->stamps);
     CWT_LAUNCH_CHECK();
     return 0;
   }
   unsigned long long* stp = nullptr;
   if (mode == 1) {  // timing study (tools/persist_stamps.py)
-    const long n_st = ((long)iters + 1) * G * 10;
+    const long n_st = ((long)p.iters + 1) * G * 10;
     if (n_st > g_adapt_stamps_n) {
       CWT_HIP(hipDeviceSynchronize());
       if (g_adapt_stamps) CWT_HIP(hipFree(g_adapt_stamps));
@@ -1772,7 +1687,7 @@ static int enqueue_adapt_persist(const float* f, const uint8_t* lbl_ws, const Ad
     case 3: CWT_PA_LAUNCH(NR, 3); break;     \
     default: CWT_PA_LAUNCH(NR, 0); break;    \
   }
-  switch (nres) {
+  switch (p.form) {
     case 6: CWT_PA_MODES(6); break;
     case 5: CWT_PA_MODES(5); break;
     case 4: CWT_PA_MODES(4); break;
@@ -1804,52 +1719,24 @@ size_t adapt_ws_sizes(int E, int n, int h, int w, int S, size_t* fws, size_t* lb
   return 0;
 }
 
-// Workgroups of the persistent inner loop launch_adapt will use for this geometry (each holds a
-// whole CU for the whole loop), 0 when it will use the per-step launches
-int adapt_persist_workgroups(int E, int n, int h, int w, int iters, int upw) {
-  int pG = 0, punits = 0, pncb = 0, pnres = 0, puc = 0;
-  const char* pe = getenv("CWT_ADAPT_PERSIST");
-  if (iters > 0 && !(pe && pe[0] == '0') && persist_geometry(E, n, h, w, upw, &pG, &punits, &pncb, &pnres, &puc) == 0)
-    return pG;
-  return 0;
-}
-
-// Which inner-loop kernel launch_adapt will use for this geometry (profile record names):
-// "adapt_persist_kernel<NRES" or "adapt_step_kernel<"
-const char* adapt_kernel_name(int E, int n, int h, int w, int iters, int upw) {
-  int pG = 0, punits = 0, pncb = 0, pnres = 0, puc = 0;
-  const char* pe = getenv("CWT_ADAPT_PERSIST");
-  if (iters > 0 && !(pe && pe[0] == '0') && persist_geometry(E, n, h, w, upw, &pG, &punits, &pncb, &pnres, &puc) == 0) {
-    static const char* names[7] = {"adapt_persist_kernel<0", "adapt_persist_kernel<1", "adapt_persist_kernel<2",
-                                   "adapt_persist_kernel<3", "adapt_persist_kernel<4", "adapt_persist_kernel<5",
-                                   "adapt_persist_kernel<6"};
-    return names[pnres <= 6 ? pnres : 0];
-  }
-  return "adapt_step_kernel<";
-}
-
-// E episodes of n shots each: f [E][n][h][w][512], lbl64 [E][n][S][S], W [E][2][512].
-int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int w, int S, float lr, int iters,
-                 float* W, float* f_ws /*[E][n][h][w][512]*/, uint8_t* lbl_ws, AdaptScalars* sc /*[E] + partial counts*/,
-                 float* acc3 /*[E][3][R][512]*/, float* wbuf /*[E][2][2][512]*/, AdaptDevArgs* dargs /*[E]*/,
-                 AdaptGraphCache* cache, int upw, unsigned* status, long spin_limit, hipStream_t st,
+// The plan's E episodes of n shots each: f [E][n][h][w][512], lbl64 [E][n][S][S], W [E][2][512].
+int launch_adapt(const AdaptPlan& plan, const float* f, const int64_t* lbl64, int S, float lr, float* W,
+                 const AdaptWs& ws, AdaptGraphCache* cache, unsigned* status, long spin_limit, hipStream_t st,
                  hipEvent_t ev_k0, hipEvent_t ev_k1, const FusedTail* tail) {
+  const int E = plan.E, n = plan.n, h = plan.h, w = plan.w, iters = plan.iters;
+  const bool persist = plan.persist;
   const long total = (long)n * S * S;  // labels per episode
-  unsigned long long* part = (unsigned long long*)(sc + E);  // [E][PREP_MAXBLK][2] after the scalars
+  unsigned long long* part = (unsigned long long*)(ws.sc + E);  // [E][PREP_MAXBLK][2] after the scalars
   unsigned* fpart = (unsigned*)(part + (long)E * 2 * PREP_MAXBLK);  // [E][PREP_MAXBLK] max |f| bits
   const int pblocks = (int)std::min<long>(PREP_MAXBLK, cdiv(total, 1024));
   const long fcount = (long)n * h * w * 512;
-  hipLaunchKernelGGL(adapt_prep_kernel, dim3(pblocks, E), dim3(1024), 0, st, lbl64, total, lbl_ws, part, f, fcount,
+  hipLaunchKernelGGL(adapt_prep_kernel, dim3(pblocks, E), dim3(1024), 0, st, lbl64, total, ws.lbl, part, f, fcount,
                      fpart);
   CWT_LAUNCH_CHECK();
-  int pG = 0, punits = 0, pncb = 0, pnres = 0, puc = 0;
-  const char* pe = getenv("CWT_ADAPT_PERSIST");
-  const bool persist = iters > 0 && !(pe && pe[0] == '0') &&
-                       persist_geometry(E, n, h, w, upw, &pG, &punits, &pncb, &pnres, &puc) == 0;
-  unsigned* cnt = (unsigned*)(acc3 + (long)E * ADAPT_ESTRIDE);
+  unsigned* cnt = (unsigned*)(ws.acc + (long)E * ADAPT_ESTRIDE);
   hipLaunchKernelGGL(adapt_setup_kernel, dim3(E), dim3(PREP_MAXBLK), 0, st, (const unsigned long long*)part, pblocks,
-                     sc, lr, 0, dargs, f, (long)n * h * w * 512, (const float*)W, W, 1024,
-                     iters > 0 ? acc3 : (float*)nullptr, ADAPT_ESTRIDE, persist ? 2 * ADAPT_SLOT : ADAPT_SLOT,
+                     ws.sc, lr, 0, ws.dargs, f, (long)n * h * w * 512, (const float*)W, W, 1024,
+                     iters > 0 ? ws.acc : (float*)nullptr, ADAPT_ESTRIDE, persist ? 2 * ADAPT_SLOT : ADAPT_SLOT,
                      (double*)nullptr,
                      persist ? cnt : (unsigned*)nullptr, persist ? PA_CNT_WORDS : 0, (const unsigned*)fpart);
   CWT_LAUNCH_CHECK();
@@ -1857,17 +1744,15 @@ int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int 
   if (tail && !persist) return fail(CWT_EARG, "fused tail: needs the persistent loop");
   if (persist) {  // one launch for all steps, f read in place (no copy, no graph)
     if (ev_k0) CWT_HIP(hipEventRecord(ev_k0, st));  // profile bracket of the kernel alone (optional)
-    const int r = enqueue_adapt_persist(f, lbl_ws, sc, acc3, cnt, dargs, E, n, h, w, S, iters, pG, punits, pncb, pnres,
-                                        puc, status, spin_limit, st, tail);
+    const int r = enqueue_adapt_persist(plan, f, ws, cnt, S, status, spin_limit, st, tail);
     if (ev_k1) CWT_HIP(hipEventRecord(ev_k1, st));
     return r;
   }
   // (the step launches: the caller records the bracket around the whole call)
   // the step graph reads f from the library's buffer (fixed address, baked into the graph)
-  if (f != f_ws)
-    CWT_HIP(hipMemcpyAsync(f_ws, f, (size_t)E * n * h * w * 512 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  const char* dbg = getenv("CWT_ADAPT_DBG");
-  if (dbg && (atoi(dbg) & 32)) {  // timing study: stamp buffer sized for G = 1 (allocated outside any capture)
+  if (f != ws.f)
+    CWT_HIP(hipMemcpyAsync(ws.f, f, (size_t)E * n * h * w * 512 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (plan.mode == 1) {  // timing study: stamp buffer sized for G = 1 (allocated outside any capture)
     const long n_st = (long)iters * cdiv(S - 1, 8 * ADAPT_CB) * (h - 1) * E * ADAPT_NSTAMP;
     if (n_st > g_adapt_stamps_n) {
       CWT_HIP(hipDeviceSynchronize());
@@ -1876,10 +1761,10 @@ int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int 
       g_adapt_stamps_n = n_st;
     }
   }
-  if (!cache) return enqueue_adapt_steps(dargs, f_ws, lbl_ws, sc, acc3, wbuf, E, n, h, w, S, iters, st);
+  if (!cache) return enqueue_adapt_steps(ws.dargs, ws.f, ws.lbl, ws.sc, ws.acc, ws.wbuf, E, n, h, w, S, iters, st);
   // graph path: one instantiated graph per (geometry, workspace pointers)
-  AdaptGraphCache::Entry key{E, n, h, w, S, iters, (const void*)f_ws, (const void*)lbl_ws, (const void*)sc,
-                             (const void*)acc3, (const void*)wbuf, (const void*)dargs, nullptr};
+  AdaptGraphCache::Entry key{E, n, h, w, S, iters, (const void*)ws.f, (const void*)ws.lbl, (const void*)ws.sc,
+                             (const void*)ws.acc, (const void*)ws.wbuf, (const void*)ws.dargs, nullptr};
   hipGraphExec_t exec = nullptr;
   for (auto& e : cache->entries)
     if (e.same(key)) exec = e.exec;
@@ -1887,7 +1772,7 @@ int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int 
     if (!cache->cap_stream) CWT_HIP(hipStreamCreateWithFlags(&cache->cap_stream, hipStreamNonBlocking));
     hipGraph_t g;
     CWT_HIP(hipStreamBeginCapture(cache->cap_stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_adapt_steps(dargs, f_ws, lbl_ws, sc, acc3, wbuf, E, n, h, w, S, iters, cache->cap_stream);
+    int rc = enqueue_adapt_steps(ws.dargs, ws.f, ws.lbl, ws.sc, ws.acc, ws.wbuf, E, n, h, w, S, iters, cache->cap_stream);
     hipError_t e2 = hipStreamEndCapture(cache->cap_stream, &g);
     if (rc) return rc;
     if (e2 != hipSuccess) return fail((int)e2, std::string("adapt graph capture: ") + hipGetErrorString(e2));

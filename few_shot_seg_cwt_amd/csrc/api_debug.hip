@@ -381,6 +381,23 @@ int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5) {
   return 0;
 }
 
+int cwt_debug_adapt_plan(int E, int n, int h, int w, int iters, int upw, int cu_count, int* out8) {
+  CWT_CHECK(out8 && E >= 1 && n >= 1 && h >= 2 && w >= 2 && upw >= 0, "bad arguments");
+  const AdaptPlan p = adapt_plan(E, n, h, w, iters, upw, cu_count, adapt_knobs_from_env());
+  const int v[8] = {p.persist ? 1 : 0, p.form, p.G, p.units, p.ncb, p.uc, (int)p.k, (int)p.span};
+  std::copy(v, v + 8, out8);
+  return 0;
+}
+
+int cwt_debug_adapt_form(int form, int* out6) {
+  CWT_CHECK(out6, "out6 is NULL");
+  if (form < 0 || form >= PA_NFORMS) return fail(CWT_EARG, "no such inner-loop form (adapt_plan.h)");
+  const PaFormTraits t = pa_form_traits(form);
+  const int v[6] = {t.nu, t.ewk, t.lock, t.breg, t.stream, t.res1};
+  std::copy(v, v + 6, out6);
+  return 0;
+}
+
 int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
                        const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,

@@ -8,6 +8,47 @@
 
 using namespace cwt;
 
+// CUs of the first device a plan is asked for (the persistent loop needs its workgroups co-resident);
+// 0 where the query fails, and the next call asks again
+static int adapt_cu_count() {
+  static int cu = 0;
+  int dev = 0;
+  if (!cu && (hipGetDevice(&dev) != hipSuccess ||
+              hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess))
+    cu = 0;
+  return cu;
+}
+
+// This call's plan of the inner loop (adapt_plan.h), made once: the launch, the profile names, the
+// fused-tail decision and the workgroup count all read it
+static AdaptPlan adapt_plan_for(cwt_ctx* ctx, int E, int n, int h, int w, int iters, const AdaptKnobs& kn) {
+  return adapt_plan(E, n, h, w, iters, ctx->adapt_upw, adapt_cu_count(), kn);
+}
+
+// The loop's workspaces
+static int adapt_ws(cwt_ctx* ctx, int E, int n, int h, int w, int S, AdaptWs* out) {
+  void *fws, *lbl, *sc, *acc, *wb, *dargs;
+  size_t b_f, b_lbl, b_sc, b_acc, b_wb, b_args;
+  adapt_ws_sizes(E, n, h, w, S, &b_f, &b_lbl, &b_sc, &b_acc, &b_wb, &b_args);
+  int rc;
+  if ((rc = ensure_ws(ctx, "adapt.f", b_f, &fws)) || (rc = ensure_ws(ctx, "adapt.args", b_args, &dargs)) ||
+      (rc = ensure_ws(ctx, "adapt.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "adapt.sc", b_sc, &sc)) ||
+      (rc = ensure_ws(ctx, "adapt.acc", b_acc, &acc)) ||  // [E][3][ADAPT_RMAX][512]
+      (rc = ensure_ws(ctx, "adapt.wbuf", b_wb, &wb)))
+    return rc;
+  *out = AdaptWs{(float*)fws, (uint8_t*)lbl, (AdaptScalars*)sc, (float*)acc, (float*)wb, (AdaptDevArgs*)dargs};
+  return 0;
+}
+
+// cwt_inner_adapt_tail fuses the tail into the loop's launch where the loop runs as the two-unit
+// register form (EpisodePipeline's adapt context) in its product instantiation
+static bool fused_tail_applies(const AdaptPlan& plan, const AdaptKnobs& kn) {
+  const char* fz = getenv("CWT_FUSED_LOOP_TAIL");
+  const char* tst = getenv("CWT_TAIL_STAMPS");
+  return plan.persist && plan.form == PA_PAIR_REG && plan.E == 1 && kn.dbg == 0 && !(fz && fz[0] == '0') &&
+         !(tst && tst[0] == '1');
+}
+
 extern "C" {
 
 int cwt_inner_adapt_batch(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int E, int n, int h, int w, int C,
@@ -18,30 +59,22 @@ int cwt_inner_adapt_batch(cwt_ctx* ctx, const float* f_s, const int64_t* s_label
   CWT_CHECK(E >= 1 && E <= 64 && n >= 1 && h >= 2 && w >= 2 && iters >= 0, "bad sizes");
   CWT_CHECK(S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1), "need S-1 == 8*(h-1) == 8*(w-1)");
   CWT_HIP(hipSetDevice(ctx->device));
-  void *fws, *lbl, *sc, *acc, *wb, *dargs;
-  size_t b_f, b_lbl, b_sc, b_acc, b_wb, b_args;
-  adapt_ws_sizes(E, n, h, w, S, &b_f, &b_lbl, &b_sc, &b_acc, &b_wb, &b_args);
+  AdaptWs aws;
   int rc;
-  if ((rc = ensure_ws(ctx, "adapt.f", b_f, &fws)) || (rc = ensure_ws(ctx, "adapt.args", b_args, &dargs)) ||
-      (rc = ensure_ws(ctx, "adapt.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "adapt.sc", b_sc, &sc)) ||
-      (rc = ensure_ws(ctx, "adapt.acc", b_acc, &acc)) ||  // [E][3][ADAPT_RMAX][512]
-      (rc = ensure_ws(ctx, "adapt.wbuf", b_wb, &wb)))
-    return rc;
+  if ((rc = adapt_ws(ctx, E, n, h, w, S, &aws))) return rc;
+  const AdaptPlan plan = adapt_plan_for(ctx, E, n, h, w, iters, adapt_knobs_from_env());
+  const char* kname = adapt_plan_kernel_name(plan);
   // algorithmic work: per step 2 x (2*2*C*h*w*n) FLOPs; minimal bytes = f_s + labels once per step
   Prof p(ctx, (hipStream_t)stream,
-         "inner_adapt x" + std::to_string(iters) + (E > 1 ? " E=" + std::to_string(E) : "") + " [" +
-             adapt_kernel_name(E, n, h, w, iters, ctx->adapt_upw) + "]",
+         "inner_adapt x" + std::to_string(iters) + (E > 1 ? " E=" + std::to_string(E) : "") + " [" + kname + "]",
          (double)E * iters * 2.0 * (4.0 * C * h * w * n), (double)E * iters * ((double)n * h * w * C * 4 + (double)n * S * S),
          1);
   // the persistent kernel alone (no label prep / setup kernels): the launch rocprofv3 times
-  const char* kname = adapt_kernel_name(E, n, h, w, iters, ctx->adapt_upw);
-  const bool persist_k = strncmp(kname, "adapt_persist", 13) == 0;
   Prof pk(ctx, (hipStream_t)stream, std::string("inner_adapt_kernel [") + kname + "]",
           (double)E * iters * 2.0 * (4.0 * C * h * w * n), (double)E * iters * ((double)n * h * w * C * 4 + (double)n * S * S),
-          1, persist_k);
-  rc = launch_adapt(f_s, s_label, E, n, h, w, S, lr, iters, W_inout, (float*)fws, (uint8_t*)lbl, (AdaptScalars*)sc,
-                    (float*)acc, (float*)wb, (AdaptDevArgs*)dargs, ctx->use_graph ? &ctx->adapt_graphs : nullptr,
-                    ctx->adapt_upw, ctx->status_dev, ctx->adapt_spin_limit, (hipStream_t)stream, pk.ev0(), pk.ev1());
+          1, plan.persist);
+  rc = launch_adapt(plan, f_s, s_label, S, lr, W_inout, aws, ctx->use_graph ? &ctx->adapt_graphs : nullptr,
+                    ctx->status_dev, ctx->adapt_spin_limit, (hipStream_t)stream, pk.ev0(), pk.ev1());
   p.end();
   return rc;
 }
@@ -208,17 +241,6 @@ int cwt_episode_tail(cwt_ctx* ctx, const float* q, const float* f, int B, int h,
   return rc;
 }
 
-// cwt_inner_adapt_tail fuses the tail into the loop's launch where the loop runs as the two-unit
-// register form (EpisodePipeline's adapt context) in its product instantiation
-static bool fused_tail_applies(cwt_ctx* ctx, int n, int h, int w, int iters) {
-  const char* kname = adapt_kernel_name(1, n, h, w, iters, ctx->adapt_upw);
-  const char* dbg = getenv("CWT_ADAPT_DBG");
-  const char* fz = getenv("CWT_FUSED_LOOP_TAIL");
-  const char* tst = getenv("CWT_TAIL_STAMPS");
-  return strcmp(kname, "adapt_persist_kernel<5") == 0 && !(dbg && atoi(dbg) != 0) && !(fz && fz[0] == '0') &&
-         !(tst && tst[0] == '1');
-}
-
 int cwt_inner_adapt_tail(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w, int C, int S,
                          float lr, int iters, float* W_inout, const float* f_q, const int64_t* q_label,
                          const float* w_qkvs, const float* fc_w, const float* fc_b, const float* ln_w,
@@ -234,7 +256,9 @@ int cwt_inner_adapt_tail(cwt_ctx* ctx, const float* f_s, const int64_t* s_label,
   CWT_HIP(hipSetDevice(ctx->device));
   // fused where the loop runs as the two-unit register form (EpisodePipeline's adapt context) in
   // its product instantiation; everything else (and CWT_FUSED_LOOP_TAIL=0) runs the two calls
-  if (!fused_tail_applies(ctx, n, h, w, iters)) {
+  const AdaptKnobs knobs = adapt_knobs_from_env();
+  const AdaptPlan plan = adapt_plan_for(ctx, 1, n, h, w, iters, knobs);
+  if (!fused_tail_applies(plan, knobs)) {
     int rc = cwt_inner_adapt(ctx, f_s, s_label, n, h, w, C, S, lr, iters, W_inout, stream);
     if (rc) return rc;
     return cwt_episode_tail(ctx, W_inout, f_q, 1, h, w, S, q_label, w_qkvs, fc_w, fc_b, ln_w, ln_b, params_version, out,
@@ -243,17 +267,11 @@ int cwt_inner_adapt_tail(cwt_ctx* ctx, const float* f_s, const int64_t* s_label,
   const hipStream_t st = (hipStream_t)stream;
   constexpr int H = 4;
   const int hw = h * w;
-  const int G = adapt_persist_workgroups(1, n, h, w, iters, ctx->adapt_upw);
+  const int G = plan.G;  // the tail runs on the loop's workgroups
   CWT_CHECK(G >= 1 && G <= 512, "fused tail: loop geometry");
-  // the loop's workspaces (cwt_inner_adapt_batch)
-  void *fws, *lbl, *sc, *acc, *wb, *dargs;
-  size_t b_f, b_lbl, b_sc, b_acc, b_wb, b_args;
-  adapt_ws_sizes(1, n, h, w, S, &b_f, &b_lbl, &b_sc, &b_acc, &b_wb, &b_args);
+  AdaptWs aws;
   int rc;
-  if ((rc = ensure_ws(ctx, "adapt.f", b_f, &fws)) || (rc = ensure_ws(ctx, "adapt.args", b_args, &dargs)) ||
-      (rc = ensure_ws(ctx, "adapt.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "adapt.sc", b_sc, &sc)) ||
-      (rc = ensure_ws(ctx, "adapt.acc", b_acc, &acc)) || (rc = ensure_ws(ctx, "adapt.wbuf", b_wb, &wb)))
-    return rc;
+  if ((rc = adapt_ws(ctx, 1, n, h, w, S, &aws))) return rc;
   // the tail's (cwt_episode_tail), over the loop's G workgroups
   float *fold, *tws, *wq;
   unsigned* cnt;
@@ -300,9 +318,8 @@ int cwt_inner_adapt_tail(cwt_ctx* ctx, const float* f_s, const int64_t* s_label,
   // the launch's loop part and tail part (its stamps; the events only order the read-back)
   Prof pk(ctx, st, "inner_adapt_kernel [" + kn + "]", lfl, lby, 1, true);
   if (pk.idx >= 0) ctx->recs[pk.idx].fslot = slot;
-  rc = launch_adapt(f_s, s_label, 1, n, h, w, S, lr, iters, W_inout, (float*)fws, (uint8_t*)lbl, (AdaptScalars*)sc,
-                    (float*)acc, (float*)wb, (AdaptDevArgs*)dargs, nullptr, ctx->adapt_upw, ctx->status_dev,
-                    ctx->adapt_spin_limit, st, pk.ev0(), pk.ev1(), &ft);
+  rc = launch_adapt(plan, f_s, s_label, S, lr, W_inout, aws, nullptr, ctx->status_dev, ctx->adapt_spin_limit, st,
+                    pk.ev0(), pk.ev1(), &ft);
   p.end();
   if (rc) return rc;
   for (const char* tn : {"post_loop_tail", "episode_tail_kernel"}) {
@@ -457,14 +474,15 @@ int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int
 int cwt_adapt_workgroups(cwt_ctx* ctx, int E, int n, int h, int w, int iters, int* G) {
   if (!ctx || !G || E < 1 || n < 1 || h < 2 || w < 2) return fail(CWT_EARG, "bad arguments");
   CWT_HIP(hipSetDevice(ctx->device));
-  *G = adapt_persist_workgroups(E, n, h, w, iters, ctx->adapt_upw);
+  *G = adapt_plan_for(ctx, E, n, h, w, iters, adapt_knobs_from_env()).G;
   return 0;
 }
 
 int cwt_adapt_fuses_tail(cwt_ctx* ctx, int n, int h, int w, int iters, int* fused) {
   if (!ctx || !fused || n < 1 || h < 2 || w < 2 || iters < 0) return fail(CWT_EARG, "bad arguments");
   CWT_HIP(hipSetDevice(ctx->device));
-  *fused = fused_tail_applies(ctx, n, h, w, iters) ? 1 : 0;
+  const AdaptKnobs kn = adapt_knobs_from_env();
+  *fused = fused_tail_applies(adapt_plan_for(ctx, 1, n, h, w, iters, kn), kn) ? 1 : 0;
   return 0;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 
+#include "adapt_plan.h"
 #include "common.h"
 
 namespace cwt {
@@ -289,12 +290,19 @@ int launch_unsplit_act(const __bf16* s, long P, int C, float* out, int ld, hipSt
 int launch_widen_bf16(const __bf16* x, long n, float* y, hipStream_t st);
 
 // ---- adapt.hip ----
-int launch_adapt(const float* f, const int64_t* lbl64, int E, int n, int h, int w, int S, float lr, int iters,
-                 float* W, float* f_ws, uint8_t* lbl_ws, AdaptScalars* sc, float* acc3, float* wbuf,
-                 AdaptDevArgs* dargs, AdaptGraphCache* cache, int upw, unsigned* status, long spin_limit,
-                 hipStream_t st, hipEvent_t ev_k0, hipEvent_t ev_k1, const FusedTail* tail = nullptr);
-const char* adapt_kernel_name(int E, int n, int h, int w, int iters, int upw);
-int adapt_persist_workgroups(int E, int n, int h, int w, int iters, int upw);
+// the loop's workspaces (sizes: adapt_ws_sizes)
+struct AdaptWs {
+  float* f;             // [E][n][h][w][512]: the step launches' copy of f
+  uint8_t* lbl;         // [E][n][S][S]
+  AdaptScalars* sc;     // [E] + partial counts
+  float* acc;           // [E][3][R][512] + the persistent loop's counters
+  float* wbuf;          // [E][2][2][512]
+  AdaptDevArgs* dargs;  // [E]
+};
+// the launch plan names (adapt_plan.h); the geometry is the plan's
+int launch_adapt(const AdaptPlan& plan, const float* f, const int64_t* lbl64, int S, float lr, float* W,
+                 const AdaptWs& ws, AdaptGraphCache* cache, unsigned* status, long spin_limit, hipStream_t st,
+                 hipEvent_t ev_k0, hipEvent_t ev_k1, const FusedTail* tail = nullptr);
 extern unsigned long long* g_adapt_stamps;
 extern long g_adapt_stamps_n;
 size_t adapt_ws_sizes(int E, int n, int h, int w, int S, size_t* fws, size_t* lbl, size_t* sc, size_t* acc,

@@ -79,6 +79,18 @@ int cwt_debug_conv_x6(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int C
 int cwt_debug_conv_form(int prec, int bm, int bn, int var, int* out4);
 int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5);
 
+/* The inner loop's launch plan (csrc/adapt_plan.h), on the host alone (no context, no device call;
+ * the CWT_ADAPT_* knobs are read from the environment as cwt_inner_adapt reads them).  For E
+ * episodes of n shots of h x w features, iters steps, the context's units per workgroup upw
+ * (cwt_ctx_set_adapt_units; 0 none) on a device of cu_count CUs -> out8 = persist (1 one persistent
+ * launch, 0 the per-step launches: then form is -1 and the rest 0), form (the kernel's NRES, 0..6),
+ * G workgroups, units, ncb column blocks per row pair, uc columns per unit, k units per workgroup
+ * at most, span episodes a workgroup's units touch at most.
+ * cwt_debug_adapt_form: the traits of persistent form 0..6 -> out6 = units in lockstep, episodes a
+ * workgroup may span, lock, breg, stream, res1 (PaFormTraits); CWT_EARG for any other form. */
+int cwt_debug_adapt_plan(int E, int n, int h, int w, int iters, int upw, int cu_count, int* out8);
+int cwt_debug_adapt_form(int form, int* out6);
+
 /* The same conv in the Winograd F(2x2, 3x3) form on the x6 arithmetic (wino.hip; the form the
  * x6 stack takes for stride-1 3x3 layers with Ci >= 256): k == 3, stride 1, pad == dil; the weights
  * are transformed and split on the device each call; bm / bn pick the 16 batched GEMMs' tile

@@ -59,8 +59,8 @@ def _run(persist, f, lbl, W0, iters, uc=None, upw=None, stream=None, res1=None):
 
 
 @pytest.mark.parametrize("E,n,S,iters,uc", [
-    (1, 1, 473, 200, None),  # config #2: 236 15-column units, one per workgroup (f resident in registers)
-    (1, 1, 473, 200, "31"),  # ... as 118 31-column units
+    (1, 1, 473, 200, None),  # config #2: 118 31-column units, one per workgroup (f resident in registers)
+    (1, 1, 473, 200, "31"),  # ... with the column count named (the same geometry)
     (1, 5, 473, 200, None),  # config #3: 590 units, three per workgroup in lockstep (197 workgroups)
     (8, 5, 129, 20, None),   # 640 units, three per workgroup, workgroups spanning two episodes
     (1, 1, 641, 200, None),  # config #4 shapes: 240 units
