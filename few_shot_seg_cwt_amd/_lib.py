@@ -134,6 +134,9 @@ SIGNATURES = {
     "cwt_debug_conv_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_adapt_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_adapt_form": (_I, [_I, C.POINTER(_I)]),
+    "cwt_debug_extract_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I64]),
+    "cwt_debug_extract_mode": (_I, [_I, C.POINTER(_I)]),
+    "cwt_debug_backbone_arch": (_I, [_I, C.c_char_p, _I64]),
     "cwt_debug_census": (_I, [_P, _I, _P, _P]),
     "cwt_debug_tail_stamps": (_I, [_P, _P, _I64, _P]),
     "cwt_debug_occupy": (_I, [_P, _I, _I, _P]),

@@ -80,6 +80,13 @@ static int debug_conv_s(cwt_ctx* ctx, int prec, const void* xs, int N, int Hi, i
   return launch_conv_x3s(a, p, 0, part, pf, (hipStream_t)stream, prec);
 }
 
+// A text export into the caller's buffer (NUL-terminated)
+static int copy_text(const std::string& text, char* buf, int64_t cap) {
+  CWT_CHECK(buf && (int64_t)text.size() + 1 <= cap, "text buffer too small");
+  memcpy(buf, text.c_str(), text.size() + 1);
+  return 0;
+}
+
 extern "C" {
 
 int cwt_debug_conv(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, int x_ld, const float* w_packed,
@@ -90,24 +97,25 @@ int cwt_debug_conv(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, 
   CWT_CHECK(x && w_packed && scale && shift && y, "null buffer");
   CWT_CHECK(Ci % 32 == 0 && Co % 64 == 0 && x_ld >= Ci && y_ld >= y_off + Co, "need Ci%32==0, Co%64==0");
   CWT_HIP(hipSetDevice(ctx->device));
-  ConvLayer L;
-  L.Ci = Ci;
-  L.Co = Co;
-  L.k = k;
-  L.stride = stride;
-  L.pad = pad;
-  L.dil = dil;
-  L.w = (float*)w_packed;
   int rc;
   if (k > 1) {  // caller layout [Co][k][k][Ci] -> packed_k order
-    if ((rc = ws(ctx, "dbg.wpack", (size_t)Co * k * k * Ci, &L.w))) return rc;
-    if ((rc = launch_repack_cblock(w_packed, L.w, Co, k * k, Ci, (hipStream_t)stream))) return rc;
-    w_packed = L.w;
+    float* wp;
+    if ((rc = ws(ctx, "dbg.wpack", (size_t)Co * k * k * Ci, &wp))) return rc;
+    if ((rc = launch_repack_cblock(w_packed, wp, Co, k * k, Ci, (hipStream_t)stream))) return rc;
+    w_packed = wp;
   }
-  L.scale = (float*)scale;
-  L.shift = (float*)shift;
-  ConvCall c{0, &L, x, N, Hi, Wi, x_ld, y, y_ld, y_off, res, res_ld, relu, true};
-  ConvArgs a = make_args(c);
+  ConvArgs a = conv_geom<ConvArgs>(N, Hi, Wi, Ci, Co, k, stride, pad, dil);
+  a.x = x;
+  a.x_ld = x_ld;
+  a.w = w_packed;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = res;
+  a.res_ld = res_ld;
+  a.y = y;
+  a.y_ld = y_ld;
+  a.y_off = y_off;
+  a.relu = relu;
   CWT_CHECK(precision == 0, "cwt_debug_conv runs the exact-fp32 conv only (bf16x3 plans: cwt_debug_conv_s)");
   ConvPlan p = plan_conv(a.M, a.Co, a.K);
   if (bm > 0) {
@@ -389,6 +397,52 @@ int cwt_debug_adapt_plan(int E, int n, int h, int w, int iters, int upw, int cu_
   return 0;
 }
 
+int cwt_debug_extract_plan(int layers, int N, int S, int precision, int conv_arith, int train_bn, int want_mid, char* buf,
+                           int64_t cap) {
+  CWT_CHECK(layers == 50 || layers == 101, "layers must be 50 or 101");
+  CWT_CHECK(N >= 1 && S >= 9 && (S - 1) % 8 == 0, "need N >= 1 and (S-1) % 8 == 0");
+  const ExtractKnobs kn = extract_knobs_from_env();
+  const std::vector<ConvSpec> arch = backbone_arch(layers);
+  const ExtractPlan p = extract_plan(arch, extractor_forms(arch, kn.wino4_at_load), N, S,
+                                     extract_mode(precision, conv_arith, train_bn != 0, kn), kn, want_mid ? 7 : 0,
+                                     train_bn != 0);
+  if (p.error) return fail(CWT_ESTATE, p.error);
+  std::string out;
+  char num[64];
+  for_each_record(p, [&](const ExtractRec& r) {
+    snprintf(num, sizeof(num), "\t%.17g\t%.17g\n", r.flops, r.bytes);
+    out += std::to_string(r.level) + "\t" + r.name + num;
+  });
+  const ExtractSizes& z = p.ws;
+  const std::pair<const char*, size_t> sizes[] = {
+      {"bb.A", z.A}, {"bb.B", z.A}, {"bb.T1", z.T1}, {"bb.T2", z.T2}, {"bb.D", z.D}, {"bb.COL", z.COL},
+      {"bb.POOL", z.POOL}, {"bb.PPM", z.PPM}, {"bb.Q", z.Q}, {"bb.R", z.R}, {"bb.F", z.F}, {"bb.PARTS", z.PARTS},
+      {"bb.PART", z.PART}, {"bn.part", z.bn_part}, {"wino.V", z.wino_V}, {"wino.M", z.wino_M}};
+  for (const auto& s : sizes) out += std::string("ws\t") + s.first + "\t" + std::to_string(s.second) + "\n";
+  for (const ExtractStep& s : p.steps)  // the one choice of form no record names
+    if (s.kind == XS_PPM_CONV) out += std::string("form\tppm_gemm\t") + (s.few_cells ? "few_rows" : "splitk") + "\n";
+  return copy_text(out, buf, cap);
+}
+
+int cwt_debug_extract_mode(int mode, int* out5) {
+  CWT_CHECK(out5, "out5 is NULL");
+  if (mode < 0 || mode >= EM_NMODES) return fail(CWT_EARG, "no such extractor mode (extract_plan.h)");
+  const ExtractModeTraits t = extract_mode_traits(mode);
+  const int v[5] = {t.layout, t.prec, t.dma, t.out_f32, (int)t.elem_bytes};
+  std::copy(v, v + 5, out5);
+  return 0;
+}
+
+int cwt_debug_backbone_arch(int layers, char* buf, int64_t cap) {
+  CWT_CHECK(layers == 50 || layers == 101, "layers must be 50 or 101");
+  std::string out;
+  for (const ConvSpec& s : backbone_arch(layers))
+    out += s.wname + "\t" + s.bnp + "\t" + std::to_string(s.Ci) + "\t" + std::to_string(s.Co) + "\t" +
+           std::to_string(s.k) + "\t" + std::to_string(s.stride) + "\t" + std::to_string(s.pad) + "\t" +
+           std::to_string(s.dil) + "\n";
+  return copy_text(out, buf, cap);
+}
+
 int cwt_debug_adapt_form(int form, int* out6) {
   CWT_CHECK(out6, "out6 is NULL");
   if (form < 0 || form >= PA_NFORMS) return fail(CWT_EARG, "no such inner-loop form (adapt_plan.h)");
@@ -410,8 +464,9 @@ int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int 
   CWT_CHECK(Ci % 32 == 0 && Co % 64 == 0 && N >= 1 && Hi >= 1 && Wi >= 1, "need Ci % 32 == 0, Co % 64 == 0");
   CWT_CHECK(y_ld >= y_off + Co && y_ld % 4 == 0 && y_off % 4 == 0 && (!res || res_ld % 4 == 0), "bad strides");
   int rc;
-  ConvPlan named;  // refused here, before the weights' transform is launched (run_wino_conv forces it)
-  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &named))) return rc;
+  // the form's plan, its GEMMs' tile forced where one is named: refused here, before any device call
+  WinoPlan wp = wino_plan(N, Hi, Wi, Ci, Co, dil, m, 0, 0, res != nullptr, ctx->prof_level > 0);
+  if (bm > 0 && (rc = force_conv_form(6, bm, bn, Co, &wp.gemm))) return rc;
   CWT_HIP(hipSetDevice(ctx->device));
   const hipStream_t st = (hipStream_t)stream;
   const int P = (m + 2) * (m + 2);
@@ -433,8 +488,7 @@ int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int 
     u_n = (long)n * m;
     u_dst = us;
   }
-  return run_wino_conv(ctx, x, N, Hi, Wi, Ci, Co, dil, m, us, ul, scale, shift, res, res_ld, relu, y, y_ld, y_off, 0,
-                       st, bm, bn);
+  return run_wino_conv(ctx, x, Ci, Co, wp, us, ul, scale, shift, res, res_ld, relu, y, y_ld, y_off, st);
 }
 
 int cwt_debug_conv_b16(cwt_ctx* ctx, const void* xs, int N, int Hi, int Wi, int Ci, const void* ws, const float* scale,

@@ -1,6 +1,7 @@
 // Host side of libcwt.so shared by the api*.hip units and pretrain.hip: the context (workspace
 // pool, profiler, per-context state), the fp32 GEMM helpers on the LDS-DMA conv body, and the conv
-// call description the extractor shares with the debug hooks.
+// layer and Winograd conv the extractor shares with the debug hooks (the extractor's geometry and
+// plan: extract_plan.h; the architecture: backbone_arch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 
 #include "../../include/cwt.h"
 #include "common.h"
+#include "extract_plan.h"
 #include "kernels.h"
 
 namespace cwt {
@@ -115,6 +117,11 @@ struct Prof {
   }
 };
 
+// The bracket of a planned record (ExtractRec, extract_plan.h; level 0: none at any profile level)
+static inline Prof open_record(cwt_ctx* ctx, hipStream_t st, const ExtractRec& r) {
+  return Prof(ctx, st, r.name, r.flops, r.bytes, r.level > 0 ? r.level : 1 << 30);
+}
+
 // The context's named workspace pool (api.hip): a buffer grows (256-B rounding, after a device
 // synchronise) and never shrinks; ws<T> is ensure_ws with the size in elements of T
 int ensure_ws(cwt_ctx* ctx, const std::string& name, size_t bytes, void** out);
@@ -136,20 +143,12 @@ int readout_gemm(cwt_ctx* ctx, const float* P, const float* vt, int B, int NA, i
                  hipStream_t st);
 int gemm_nt(cwt_ctx* ctx, const float* A, const float* W, int M, int N, int K, float* C, hipStream_t st);
 
-static const int kBlocks50[4] = {3, 4, 6, 3};
-static const int kBlocks101[4] = {3, 4, 23, 3};
-static const int kBins[4] = {1, 2, 3, 6};
-
-static inline int down2(int x) { return (x - 1) / 2 + 1; }  // 3x3 s2 p1 conv / maxpool output size
 static inline long ld32(long n) { return (n + 31) & ~31L; }
 
-static inline int conv_out_size(int in, int k, int stride, int pad, int dil) {
-  return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-}
-
-// A zeroed ConvSArgs with the conv's geometry, M and K set
-static inline ConvSArgs conv_s_geom(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dil) {
-  ConvSArgs a;
+// A zeroed ConvSArgs / ConvArgs with the conv's geometry, M and K set (down2, conv_out_size: extract_plan.h)
+template <class Args>
+static inline Args conv_geom(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dil) {
+  Args a;
   memset(&a, 0, sizeof(a));
   a.N = N;
   a.Hi = Hi;
@@ -166,8 +165,11 @@ static inline ConvSArgs conv_s_geom(int N, int Hi, int Wi, int Ci, int Co, int k
   a.K = k * k * Ci;
   return a;
 }
+static inline ConvSArgs conv_s_geom(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dil) {
+  return conv_geom<ConvSArgs>(N, Hi, Wi, Ci, Co, k, stride, pad, dil);
+}
 
-// ---- the extractor's conv description (api_extract.hip), shared with the debug hooks ----
+// ---- the extractor's conv layers (api_extract.hip), shared with the debug hooks ----
 struct ConvLayer {
   int Ci = 0, Co = 0, k = 1, stride = 1, pad = 0, dil = 1;
   float* w = nullptr;  // device, packed [Co][k][k][Ci] (stem conv1: [ci][ky][kx][co])
@@ -186,23 +188,6 @@ struct ConvLayer {
   float* bn = nullptr;  // [4][Co] gamma, beta, running_mean, running_var (training-mode BN)
 };
 
-struct ConvCall {
-  int stage;  // 0 stem, 1-4 layer1-4, 5 PPM, 6 bottleneck (kernel symbol tag)
-  const ConvLayer* L;
-  const float* x;
-  int N, Hi, Wi, x_ld;
-  float* y;
-  int y_ld, y_off;
-  const float* res;
-  int res_ld;
-  int relu;
-  bool out_f32;  // S-layout mode: this call writes fp32 (and takes an fp32 residual)
-  // x6: the second A source of a block's fused conv3 + downsample conv (L = Block::fused, Ci2 more
-  // input channels read from x2 [N][Hi2][Wi2][Ci2] at stride2; ConvSArgs::xs2), nullptr: a plain conv
-  const float* x2 = nullptr;
-  int Hi2 = 0, Wi2 = 0, Ci2 = 0, stride2 = 0;
-};
-
 // The input of a Winograd conv still in its producer's split-K partial planes (x = part
 // [nsplit][N*H*W][Ci]): the input transform sums them and applies the producer's BN and ReLU itself
 struct WinoSplitKSrc {
@@ -211,11 +196,10 @@ struct WinoSplitKSrc {
   int relu;
 };
 
-ConvArgs make_args(const ConvCall& c);
 int force_conv_form(int prec, int bm, int bn, int Co, ConvPlan* p);
-int run_wino_conv(cwt_ctx* ctx, const float* x, int N, int H, int W, int Ci, int Co, int d, int m, const __bf16* us,
-                  const __bf16* ul, const float* scale, const float* shift, const float* res, int res_ld, int relu,
-                  float* y, int y_ld, int y_off, int stage, hipStream_t st, int bm = 0, int bn = 0,
-                  const WinoSplitKSrc* sk = nullptr);
+// One Winograd conv as wp plans it (wino_plan, extract_plan.h: geometry, GEMM plan, sub-records)
+int run_wino_conv(cwt_ctx* ctx, const float* x, int Ci, int Co, const WinoPlan& wp, const __bf16* us, const __bf16* ul,
+                  const float* scale, const float* shift, const float* res, int res_ld, int relu, float* y, int y_ld,
+                  int y_off, hipStream_t st, const WinoSplitKSrc* sk = nullptr);
 
 }  // namespace cwt

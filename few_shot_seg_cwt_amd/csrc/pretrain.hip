@@ -142,16 +142,15 @@ struct PtBuilder {
     pt->params.push_back(p);
     return (int)pt->params.size() - 1;
   }
-  void conv(PtConv& L, const std::string& wname, const std::string& bnp, int Ci, int Co, int k, int stride, int pad,
-            int dil, bool stem1 = false) {
-    L.Ci = Ci;
-    L.Co = Co;
-    L.k = k;
-    L.stride = stride;
-    L.pad = pad;
-    L.dil = dil;
-    L.w_off = pt->params[add(wname, (long)Co * Ci * k * k, stem1 ? PT_STEM1 : PT_CONV, Co, Ci, k)].off;
-    bn(L.bn, bnp, Co);
+  void conv(PtConv& L, const ConvSpec& s, bool stem1 = false) {
+    L.Ci = s.Ci;
+    L.Co = s.Co;
+    L.k = s.k;
+    L.stride = s.stride;
+    L.pad = s.pad;
+    L.dil = s.dil;
+    L.w_off = pt->params[add(s.wname, (long)s.Co * s.Ci * s.k * s.k, stem1 ? PT_STEM1 : PT_CONV, s.Co, s.Ci, s.k)].off;
+    bn(L.bn, s.bnp, s.Co);
   }
   void bn(PtBn& b, const std::string& bnp, int C) {
     b.C = C;
@@ -161,44 +160,33 @@ struct PtBuilder {
   }
 };
 
+// The parameters in the order of the architecture's table (backbone_arch.h), then the classifier
 static int pt_build(cwt_pretrain* pt) {
   PtBuilder B{pt};
-  B.conv(pt->stem[0], "layer0.0.weight", "layer0.1", 3, 64, 3, 2, 1, 1, true);
-  B.conv(pt->stem[1], "layer0.3.weight", "layer0.4", 64, 64, 3, 1, 1, 1);
-  B.conv(pt->stem[2], "layer0.6.weight", "layer0.7", 64, 128, 3, 1, 1, 1);
-  const int* nb = pt->layers == 50 ? kBlocks50 : kBlocks101;
-  const int planes_of[4] = {64, 128, 256, 512};
-  int inplanes = 128;
-  for (int li = 0; li < 4; ++li) {
-    const int planes = planes_of[li];
-    for (int bi = 0; bi < nb[li]; ++bi) {
-      PtBlock blk;
-      int s2 = 1, d2 = 1, sd = 1;  // dilation surgery (pspnet.py:103-112)
-      if (li == 1 && bi == 0) s2 = sd = 2;
-      if (li == 2) d2 = 2;
-      if (li == 3) d2 = 4;
-      const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-      B.conv(blk.c1, p + ".conv1.weight", p + ".bn1", inplanes, planes, 1, 1, 0, 1);
-      B.conv(blk.c2, p + ".conv2.weight", p + ".bn2", planes, planes, 3, s2, d2, d2);
-      B.conv(blk.c3, p + ".conv3.weight", p + ".bn3", planes, planes * 4, 1, 1, 0, 1);
-      if (bi == 0) {
-        blk.has_down = true;
-        B.conv(blk.down, p + ".downsample.0.weight", p + ".downsample.1", inplanes, planes * 4, 1, sd, 0, 1);
-      }
-      inplanes = planes * 4;
-      pt->blocks[li].push_back(blk);
+  for (const ConvSpec& s : backbone_arch(pt->layers)) {
+    switch (s.role) {
+      case ROLE_STEM: B.conv(pt->stem[s.bi], s, s.bi == 0); break;
+      case ROLE_C1:
+        pt->blocks[s.li].emplace_back();
+        B.conv(pt->blocks[s.li].back().c1, s);
+        break;
+      case ROLE_C2: B.conv(pt->blocks[s.li].back().c2, s); break;
+      case ROLE_C3: B.conv(pt->blocks[s.li].back().c3, s); break;
+      case ROLE_DOWN:
+        pt->blocks[s.li].back().has_down = true;
+        B.conv(pt->blocks[s.li].back().down, s);
+        break;
+      case ROLE_PPM:
+        if (s.bi == 0) pt->n_bb = B.off;  // the backbone's parameters end here
+        // the PPM 1x1 conv keeps PyTorch's [512][2048] layout (few-row GEMMs, not the conv kernel)
+        pt->ppm[s.bi].Ci = s.Ci;
+        pt->ppm[s.bi].Co = s.Co;
+        pt->ppm[s.bi].w_off = pt->params[B.add(s.wname, (long)s.Co * s.Ci, PT_PLAIN)].off;
+        B.bn(pt->ppm[s.bi].bn, s.bnp, s.Co);
+        break;
+      case ROLE_BOTT: B.conv(pt->bott, s); break;  // over all 4096 channels: layer4 and the PPM concat
     }
   }
-  pt->n_bb = B.off;
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "ppm.features." + std::to_string(i);
-    // the PPM 1x1 conv keeps PyTorch's [512][2048] layout (few-row GEMMs, not the conv kernel)
-    pt->ppm[i].Ci = 2048;
-    pt->ppm[i].Co = 512;
-    pt->ppm[i].w_off = pt->params[B.add(p + ".1.weight", 512L * 2048, PT_PLAIN)].off;
-    B.bn(pt->ppm[i].bn, p + ".2", 512);
-  }
-  B.conv(pt->bott, "bottleneck.0.weight", "bottleneck.1", 4096, 512, 3, 1, 1, 1);
   pt->cls_off = pt->params[B.add("classifier.weight", (long)pt->nc * 512, PT_PLAIN)].off;
   pt->n_all = B.off;
   return 0;

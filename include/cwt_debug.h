@@ -91,6 +91,27 @@ int cwt_debug_conv_plan(int prec, int M, int Co, int K, int batch, int* out5);
 int cwt_debug_adapt_plan(int E, int n, int h, int w, int iters, int upw, int cu_count, int* out8);
 int cwt_debug_adapt_form(int form, int* out6);
 
+/* The extractor's plan of one pass (csrc/extract_plan.h), on the host alone: no context, no device
+ * call, no loaded backbone (the architecture is csrc/backbone_arch.h's, the operand forms those the
+ * loader would build); the CWT_CONV_F32D / CWT_WINO / CWT_FUSE_DOWN / CWT_FUSE_SPLITK_WINO /
+ * CWT_PPM_SPLITK knobs are read from the environment as cwt_extract_features reads them.  For a
+ * ResNet-`layers` backbone of `precision` (CWT_CONV_FP32 / CWT_CONV_BF16) under a context of
+ * `conv_arith` (CWT_CONV_ARITH_*), train_bn != 0 the pass of cwt_extract_features_train_bn, want_mid
+ * != 0 that of cwt_extract_features_mid with all three layers: buf (cap bytes, NUL-terminated;
+ * CWT_EARG if too small) receives the pass's profile records in the order a pass at profile level 3
+ * takes them, one line "level\tname\tflops\tbytes" each (numbers as %.17g; a pass at level L takes the
+ * lines of level <= L), then the workspace sizes in floats as lines "ws\tname\tcount", then
+ * "form\tppm_gemm\tfew_rows|splitk" (the form of the two PPM GEMMs, which no record names).
+ * cwt_debug_extract_mode: the traits of conv family 0..4 (ExtractMode: f32, f32d, x6, x3s, b16) ->
+ * out5 = activation layout (0 fp32 NHWC, 1 S-layout, 2 bf16 NHWC), prec, on the LDS-DMA body, every
+ * conv writes fp32, bytes per element of the accounting; CWT_EARG for any other mode.
+ * cwt_debug_backbone_arch: the architecture's conv + BatchNorm pairs in order, one line
+ * "weight name\tBN prefix\tCi\tCo\tk\tstride\tpad\tdil" each. */
+int cwt_debug_extract_plan(int layers, int N, int S, int precision, int conv_arith, int train_bn, int want_mid,
+                           char* buf, int64_t cap);
+int cwt_debug_extract_mode(int mode, int* out5);
+int cwt_debug_backbone_arch(int layers, char* buf, int64_t cap);
+
 /* The same conv in the Winograd F(2x2, 3x3) form on the x6 arithmetic (wino.hip; the form the
  * x6 stack takes for stride-1 3x3 layers with Ci >= 256): k == 3, stride 1, pad == dil; the weights
  * are transformed and split on the device each call; bm / bn pick the 16 batched GEMMs' tile
