@@ -404,7 +404,8 @@ int cwt_debug_extract_plan(int layers, int N, int S, int precision, int conv_ari
   const ExtractKnobs kn = extract_knobs_from_env();
   const std::vector<ConvSpec> arch = backbone_arch(layers);
   const ExtractPlan p = extract_plan(arch, extractor_forms(arch, kn.wino4_at_load), N, S,
-                                     extract_mode(precision, conv_arith, train_bn != 0, kn), kn, want_mid ? 7 : 0,
+                                     extract_mode(precision, conv_arith, train_bn != 0, kn), kn,
+                                     extract_last_blocks(arch, want_mid ? 7 : 0),
                                      train_bn != 0);
   if (p.error) return fail(CWT_ESTATE, p.error);
   std::string out;
@@ -500,7 +501,8 @@ int cwt_debug_conv_b16(cwt_ctx* ctx, const void* xs, int N, int Hi, int Wi, int 
 }
 
 // one CenterPivotConv4d layer (+ ReLU) on [B][NA][NB][cin] -> [B][NA][NB][cout] (launch_cp4d_layer);
-// variant 0 the automatic kernel choice, 1 never the rolling-window form, 2 only it
+// variant 0 the automatic kernel choice, 1 never the rolling-window form, 2 only it, 3 the
+// channel-chunked form (cout 10)
 int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
                          const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
                          void* stream) {

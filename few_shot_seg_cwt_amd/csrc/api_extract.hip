@@ -401,12 +401,13 @@ struct ExtractRun {
   const TrainBn* tb;
   hipStream_t st;
   float* buf[XB_COUNT] = {};  // XB_NONE stays null
+  float* mid[64] = {};        // the caller's buffer per requested block (ExtractStep::mid_slot)
   float *bn_part = nullptr, *bn_sc = nullptr;
   const __bf16* zero = nullptr;
   const ConvLayer* layer(int spec) const { return layer_of(bb, bb->arch[spec]); }
 };
 
-static int resolve_buffers(ExtractRun& r, const float* img, float* feat, float* const* mid) {
+static int resolve_buffers(ExtractRun& r, const float* img, float* feat) {
   const ExtractSizes& z = r.P.ws;
   cwt_ctx* ctx = r.ctx;
   float** b = r.buf;
@@ -427,7 +428,6 @@ static int resolve_buffers(ExtractRun& r, const float* img, float* feat, float* 
   if (z.wino_V && ((rc = ws(ctx, "wino.V", z.wino_V, &V)) || (rc = ws(ctx, "wino.M", z.wino_M, &M)))) return rc;
   b[XB_IMG] = const_cast<float*>(img);
   b[XB_FEAT] = feat;
-  for (int i = 0; i < 3; ++i) b[XB_MID2 + i] = mid ? mid[i] : nullptr;
   return 0;
 }
 
@@ -573,16 +573,19 @@ static int run_step(const ExtractRun& r, const ExtractStep& s) {
                                  : launch_maxpool3s2(b[XB_A], N, Hs, Hs, 128, b[XB_B], H1, H1, st);
       break;
     }
-    case XS_MID_COPY:
+    case XS_MID_COPY: {
+      float* out = s.mid_slot >= 0 && s.mid_slot < 64 ? r.mid[s.mid_slot] : nullptr;
+      if (!out) return fail(CWT_ESTATE, "extract plan: a mid feature copy without its buffer");
       if (layout == ACT_SPLIT)
-        rc = launch_unsplit_act((const __bf16*)b[s.x], s.M, s.Co, b[s.y], s.Co, st);
+        rc = launch_unsplit_act((const __bf16*)b[s.x], s.M, s.Co, out, s.Co, st);
       else if (layout == ACT_BF16)
-        rc = launch_widen_bf16((const __bf16*)b[s.x], (long)s.M * s.Co, b[s.y], st);
+        rc = launch_widen_bf16((const __bf16*)b[s.x], (long)s.M * s.Co, out, st);
       else {
-        const hipError_t e = hipMemcpyAsync(b[s.y], b[s.x], (size_t)s.M * s.Co * 4, hipMemcpyDeviceToDevice, st);
+        const hipError_t e = hipMemcpyAsync(out, b[s.x], (size_t)s.M * s.Co * 4, hipMemcpyDeviceToDevice, st);
         rc = e == hipSuccess ? 0 : fail((int)e, "mid feature copy");
       }
       break;
+    }
     case XS_PPM_POOL: rc = launch_ppm(b[s.x], N, P.h, P.h, 2048, kBins, 4, b[XB_COL], b[XB_POOL], st, layout); break;
     case XS_PPM_CONV:
     case XS_PPM_FOLD: rc = run_ppm_gemm_step(r, s); break;
@@ -606,19 +609,19 @@ static int run_step(const ExtractRun& r, const ExtractStep& s) {
 // The whole extractor: plans the pass (extract_plan.h), then executes the plan's steps in order.
 // tb != null: every BN on batch statistics with running-statistic update, Dropout2d on the
 // bottleneck output (train.py:184 model.train() before the first support extraction).
-// mid (optional, eval mode only): fp32 NHWC copies of the outputs of layer2, layer3 and layer4
-// ([N][h][h][512 / 1024 / 2048]; get_feat_list's per-layer features, pspnet.py:272-287)
+// want_blocks / mid (eval mode only): bit i set = an fp32 NHWC copy of block i's output (extract_block_bit)
+// into mid[i] ([N][h][h][512 / 1024 / 2048]; get_feat_list's features, pspnet.py:272-287)
 static int run_extract(cwt_ctx* ctx, const Backbone* bb, const float* img, int N, int S, float* feat,
-                       hipStream_t st, const TrainBn* tb = nullptr, float* const* mid = nullptr) {
+                       hipStream_t st, const TrainBn* tb = nullptr, uint64_t want_blocks = 0,
+                       float* const* mid = nullptr) {
   const ExtractKnobs kn = extract_knobs_from_env();
-  int want_mid = 0;
-  for (int i = 0; i < 3 && mid; ++i) want_mid |= (mid[i] ? 1 : 0) << i;
   const ExtractPlan P = extract_plan(bb->arch, bb->forms, N, S, extract_mode(bb->precision, ctx->conv_arith, tb, kn), kn,
-                                     want_mid, tb != nullptr, ctx->prof_level > 0);
+                                     want_blocks, tb != nullptr, ctx->prof_level > 0);
   if (P.error) return fail(CWT_ESTATE, P.error);
   ExtractRun r{ctx, bb, P, tb, st};
+  for (int i = 0; i < 64 && mid; ++i) r.mid[i] = (want_blocks >> i) & 1 ? mid[i] : nullptr;
   int rc;
-  if ((rc = resolve_buffers(r, img, feat, mid))) return rc;
+  if ((rc = resolve_buffers(r, img, feat))) return rc;
   Prof whole = open_record(ctx, st, P.whole);
   for (size_t i = 0; i < P.steps.size(); ++i) {
     if (i == P.pass_steps) whole.end();  // the post-pass refolds lie outside the pass's record
@@ -689,8 +692,30 @@ int cwt_extract_features_mid(cwt_ctx* ctx, const cwt_backbone* handle, const flo
                              float* l2, float* l3, float* l4, void* stream) {
   const Backbone* bb = reinterpret_cast<const Backbone*>(handle);
   if (const int rc = check_extract_args(ctx, bb, img, feat, N, S)) return rc;
-  float* const mid[3] = {l2, l3, l4};
-  return run_extract(ctx, bb, img, N, S, feat, (hipStream_t)stream, nullptr, mid);
+  float* const lay[3] = {l2, l3, l4};
+  const uint64_t want = extract_last_blocks(bb->arch, (l2 ? 1 : 0) | (l3 ? 2 : 0) | (l4 ? 4 : 0));
+  float* mid[64] = {};
+  for (int i = 0; i < 3; ++i)
+    if (lay[i]) mid[extract_block_bit(bb->arch, i + 1, (int)bb->blocks[i + 1].size() - 1)] = lay[i];
+  return run_extract(ctx, bb, img, N, S, feat, (hipStream_t)stream, nullptr, want, mid);
+}
+
+int cwt_extract_features_blocks(cwt_ctx* ctx, const cwt_backbone* handle, const float* img, int N, int S, float* feat,
+                                int n_out, const int* layer, const int* block, float* const* out, void* stream) {
+  const Backbone* bb = reinterpret_cast<const Backbone*>(handle);
+  if (const int rc = check_extract_args(ctx, bb, img, feat, N, S)) return rc;
+  CWT_CHECK(n_out >= 0 && n_out <= 64 && (n_out == 0 || (layer && block && out)), "bad block request");
+  uint64_t want = 0;
+  float* mid[64] = {};
+  for (int i = 0; i < n_out; ++i) {
+    CWT_CHECK(layer[i] >= 2 && layer[i] <= 4 && block[i] >= 0 && out[i], "block request: layer 2..4, block >= 0, a buffer");
+    const int bit = extract_block_bit(bb->arch, layer[i] - 1, block[i]);
+    CWT_CHECK(bit >= 0 && bit < 64, "block request: the layer has no such bottleneck");
+    CWT_CHECK(!((want >> bit) & 1), "block request: a (layer, block) pair named twice");
+    want |= uint64_t(1) << bit;
+    mid[bit] = out[i];
+  }
+  return run_extract(ctx, bb, img, N, S, feat, (hipStream_t)stream, nullptr, want, mid);
 }
 
 int cwt_extract_features_train_bn(cwt_ctx* ctx, cwt_backbone* handle, const float* img, int N, int S, float* feat,

@@ -76,8 +76,9 @@ static int match_corr_forward(cwt_ctx* ctx, const float* corr, int B, int L, int
                               int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
                               void* stream, bool cv4, float* saved = nullptr) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr && nc_params && corr2d && B >= 1 && (L == 1 || L == 2) && h >= 1 && w >= 1,
-            "bad arguments (in_channel 1 or 2)");
+  CWT_CHECK(corr && nc_params && corr2d && B >= 1 && 1 <= L && L <= CWT_MATCH_MAX_L && h >= 1 && w >= 1,
+            "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
+  CWT_CHECK(!cv4 || L <= 2, "Conv4d ('cv4') layers take in_channel 1 or 2 only (CenterPivotConv4d: up to 32)");
   CWT_CHECK(!weighted_v || (v && Cv >= 1), "weighted_v needs v");
   CWT_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
@@ -101,7 +102,7 @@ static int match_corr_forward(cwt_ctx* ctx, const float* corr, int B, int L, int
   if (L == 1) {
     if ((rc = launch_mutual_matching(corr, B, (int)NA, (int)NB, 1, x0, rm, cp, cm, st))) return rc;
   } else {
-    if (mm_fuse()) {
+    if (mm_fuse() && L == 2) {
       if ((rc = launch_mutual_matching_planar2(corr, B, (int)NA, (int)NB, x0, rm, cp, cm, st))) return rc;
     } else {
       if ((rc = launch_to_channels_last(corr, B, L, P, x0, st))) return rc;
@@ -237,7 +238,8 @@ static int mm_bwd_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, MmBwdWs* w) {
 }
 
 int cwt_match_corr_saved_floats(int B, int L, int h, int w, int symmetric, int readout, int64_t* n) {
-  if (!n || B < 1 || (L != 1 && L != 2) || h < 1 || w < 1) return fail(CWT_EARG, "bad arguments");
+  if (!n || B < 1 || L < 1 || L > CWT_MATCH_MAX_L || h < 1 || w < 1)
+    return fail(CWT_EARG, "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
   *n = (int64_t)match_saved_layout(nullptr, B, L, (long)h * w, symmetric, readout, nullptr);
   return 0;
 }
@@ -255,8 +257,8 @@ int cwt_match_corr_backward(cwt_ctx* ctx, const float* corr, int B, int L, int h
                             const float* d_corr2d, const float* d_weighted_v, float* d_corr, float* d_params,
                             float* d_v, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr && nc_params && saved && d_params && B >= 1 && (L == 1 || L == 2) && h >= 1 && w >= 1,
-            "bad arguments (in_channel 1 or 2)");
+  CWT_CHECK(corr && nc_params && saved && d_params && B >= 1 && 1 <= L && L <= CWT_MATCH_MAX_L && h >= 1 && w >= 1,
+            "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
   CWT_CHECK(!d_weighted_v || (v && Cv >= 4 && Cv % 4 == 0), "d_weighted_v needs v and Cv % 4 == 0");
   CWT_CHECK(!d_v || d_weighted_v, "d_v needs d_weighted_v");
   CWT_HIP(hipSetDevice(ctx->device));

@@ -154,7 +154,7 @@ inline WinoPlan wino_plan(int N, int H, int W, int Ci, int Co, int d, int m, int
 
 enum ExtractBuf : int {  // the pass's buffers, resolved to pointers by the executor
   XB_NONE = 0, XB_IMG, XB_A, XB_B, XB_T1, XB_T2, XB_D, XB_COL, XB_POOL, XB_PPM, XB_Q, XB_R, XB_FB, XB_PARTS,
-  XB_PART, XB_FEAT, XB_MID2, XB_MID3, XB_MID4, XB_COUNT
+  XB_PART, XB_FEAT, XB_COUNT
 };
 
 enum ExtractStepKind : int {
@@ -165,7 +165,7 @@ enum ExtractStepKind : int {
   XS_CONV_WINO,    // x6: a stride-1 3x3 conv in the Winograd form
   XS_BN_TRAIN,     // training-mode BN of the raw conv output before it (residual and ReLU after it)
   XS_MAXPOOL,
-  XS_MID_COPY,     // fp32 NHWC copy of a layer's output (cwt_extract_features_mid)
+  XS_MID_COPY,     // fp32 NHWC copy of a block's output into the caller's buffer mid_slot (cwt_extract_features_mid / _blocks)
   XS_PPM_POOL,
   XS_PPM_CONV,     // PPM 1x1 conv + BN + ReLU over the pooled cells (pspnet.py:27-29)
   XS_PPM_FOLD,     // per-tap products of the bottleneck's PPM channels with the cells
@@ -201,6 +201,7 @@ struct ExtractStep {
   long y_elems = 0, rows_per_image = 0;
   bool dropout = false;  // the bottleneck's Dropout2d
   bool few_cells = false;  // XS_PPM_CONV / XS_PPM_FOLD: the few-row form (launch_ppm_gemm)
+  int mid_slot = -1;       // XS_MID_COPY: the block's bit of the request mask (extract_block_bit)
 };
 
 struct ExtractSizes {  // floats
@@ -245,7 +246,7 @@ inline ExtractSizes extract_buffer_sizes(int N, int Hs, int H1, int h) {
 struct ExtractConvs {
   std::vector<ExtractStep> convs;
   size_t n_stem = 0, n_backbone = 0;         // convs [0, n_stem) the stem's, [n_stem, n_backbone) the blocks'
-  long last_of_layer[4] = {-1, -1, -1, -1};  // conv index of each layer's last block (mid features)
+  std::vector<long> block_end;               // per block of layers 2-4, in order: the conv index of its last conv
   ExtractBuf L4 = XB_NONE;                   // layer4 output [N][h][h][2048]
   int ppm0 = 0, bott = 0;                    // specs of the first PPM conv and of the bottleneck conv
 };
@@ -296,8 +297,7 @@ inline ExtractConvs extract_conv_list(const std::vector<ConvSpec>& arch, int N, 
       }
       cc(c3, stage, arch[c3].Ci, XB_T2, Ho, other, res, res_ld, 1);
     }
-    const bool last_block = ai >= arch.size() || !is_block_role(arch[ai].role) || arch[ai].li != li;
-    if (last_block) L.last_of_layer[li] = (long)convs.size() - 1;
+    if (li >= 1) L.block_end.push_back((long)convs.size() - 1);
     std::swap(cur, other);
     H = Ho;
   }
@@ -372,11 +372,33 @@ inline void plan_conv_record(ExtractStep& c, const ExtractModeTraits& tr, bool t
                std::to_string(c.Ho);
 }
 
-// arch / forms: backbone_arch(layers) and, per spec, the forms its loader built.  want_mid: bit i set = a copy
-// of layer (2 + i)'s output.  names: build the records' name strings (off when the profiler is: no record is
+// The per-block request of mid features: one bit per bottleneck of layers 2-4 in network order (13 bits for
+// 50 layers, 30 for 101).  The bit of block bi of layer li (1 .. 3), or -1 if the architecture has no such block
+inline int extract_block_bit(const std::vector<ConvSpec>& arch, int li, int bi) {
+  int bit = 0;
+  for (const ConvSpec& s : arch) {
+    if (s.role != ROLE_C1 || s.li < 1) continue;
+    if (s.li == li && s.bi == bi) return bit;
+    ++bit;
+  }
+  return -1;
+}
+// The request of cwt_extract_features_mid: the last block of every layer (2 + i) whose bit i of want_mid is set
+inline uint64_t extract_last_blocks(const std::vector<ConvSpec>& arch, int want_mid) {
+  uint64_t m = 0;
+  int bit = 0, last[4] = {-1, -1, -1, -1};
+  for (const ConvSpec& s : arch)
+    if (s.role == ROLE_C1 && s.li >= 1) last[s.li] = bit++;
+  for (int li = 1; li < 4; ++li)
+    if (((want_mid >> (li - 1)) & 1) && last[li] >= 0) m |= uint64_t(1) << last[li];
+  return m;
+}
+
+// arch / forms: backbone_arch(layers) and, per spec, the forms its loader built.  want_blocks: bit set = a copy
+// of that block's output (extract_block_bit); 0: none, the plan of cwt_extract_features.  names: build the records' name strings (off when the profiler is: no record is
 // taken then).
 inline ExtractPlan extract_plan(const std::vector<ConvSpec>& arch, const std::vector<ConvForms>& forms, int N, int S,
-                                ExtractMode mode, const ExtractKnobs& kn, int want_mid, bool train_bn,
+                                ExtractMode mode, const ExtractKnobs& kn, uint64_t want_blocks, bool train_bn,
                                 bool names = true) {
   ExtractPlan P;
   P.mode = mode;
@@ -446,13 +468,16 @@ inline ExtractPlan extract_plan(const std::vector<ConvSpec>& arch, const std::ve
   }
   for (size_t i = 0; i < L.n_stem; ++i) add_conv(i);
   add(XS_MAXPOOL, 2, "maxpool3s2", 0.0, 4.0 * ((double)N * Hs * Hs * 128 + (double)N * H1 * H1 * 128));
+  size_t blk = 0;  // the next block of layers 2-4 to end
   for (size_t i = L.n_stem; i < L.n_backbone; ++i) {
     add_conv(i);
-    for (int li = 1; li < 4; ++li) {  // layer2 .. layer4 outputs, before the buffer is reused
-      if ((long)i != L.last_of_layer[li] || !((want_mid >> (li - 1)) & 1)) continue;
+    if (blk >= L.block_end.size() || (long)i != L.block_end[blk]) continue;
+    // a requested block's output (after the residual and ReLU), before its buffer is reused
+    if ((want_blocks >> blk) & 1) {
       ExtractStep& s = add(XS_MID_COPY, 0, nullptr, 0.0, 0.0);
-      s.x = convs[i].y, s.y = (ExtractBuf)(XB_MID2 + li - 1), s.M = convs[i].M, s.Co = convs[i].Co;
+      s.x = convs[i].y, s.mid_slot = (int)blk, s.M = convs[i].M, s.Co = convs[i].Co;
     }
+    ++blk;
   }
   add(XS_PPM_POOL, 2, "ppm_pool", 0.0, 4.0 * ((double)N * h * h * 2048 + (double)N * 50 * 2048)).x = L.L4;
   const bool few_cells = cells <= kPpmGemmMaxRows && !kn.ppm_splitk;

@@ -6,8 +6,8 @@
 // over a correlation of NA = hA*wA query positions by NB = hB*wB support positions.
 //
 // Layout: a 4-D tensor x[B][C][hA][wA][hB][wB] (torch) is held channels-last,
-// [B][a][b][C] with a = (ha, wa), b = (hb, wb) row-major: the C <= 10 channels of one (a, b)
-// pair are one contiguous run, the b positions of one a a contiguous [hB][wB][C] image.
+// [B][a][b][C] with a = (ha, wa), b = (hb, wb) row-major: the C channels of one (a, b) pair (10 inside
+// the consensus stack, 1 .. CWT_MATCH_MAX_L = 32 at its input) are one contiguous run, the b positions of one a a contiguous [hB][wB][C] image.
 //
 // CenterPivotConv4d (stride 1, kernel 3, padding 1) is two 2-D convolutions summed: conv1 over
 // the a plane for every fixed b, conv2 over the b plane for every fixed a (conv4d.py:40-62).
@@ -21,12 +21,14 @@
 // (corr * ((corr / (max_B + eps)) * (corr / (max_A + eps)))).
 #include <cstdlib>
 
+#include "../../include/cwt.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace cwt {
 
-// ---- MutualMatching (match.py:34-53), per channel of x[B][NA][NB][C] (C = 1 or 2) ----
+// ---- MutualMatching (match.py:34-53), per channel of x[B][NA][NB][C] (C = 1 or 2: the vector forms;
+// any other C: the scalar forms below) ----
 // row maxima (over b for each a) and per-row-block partial column maxima; a thread reads the C
 // channels of a pair as one vector (both channels of a 128-B line in the same block)
 constexpr int MM_RB = 16;  // rows of a per block (the scalar form)
@@ -565,6 +567,331 @@ __global__ __launch_bounds__(256) void cp4d_wgrad_mfma_kernel(const float* __res
   }
 }
 
+// ---- the first consensus layer L -> 10 for any L up to CWT_MATCH_MAX_L (MMN with every
+// bottleneck's correlation as a channel: 9, 13, 26, 30), forward, input gradient and weight
+// gradient.  The kernels above stage all CIN channels of a tile (CmLds<CIN>: 46 KB at 10, 147 KB
+// at 32), so these walk the channels in chunks of NC_CK = 8: 9 taps x 8 channels = 72 K rows, 18
+// MFMAs per branch with no K padding, and two staged boxes of 8 x 592 floats = 37,888 B per
+// workgroup (four workgroups per CU by LDS).  A box is held channel-major, xa[c][ah][bt] and
+// xb[c][at][bh], planes NC_PL = 576 + 16 floats apart: the lane (row r, k group g4) of an MFMA
+// operand reads plane g4 at r, bank 16 g4 + r (no conflict on the a box).  Channels at or past L
+// and positions off the map are staged as 0, every global access guarded, so odd L and the last
+// partial chunk need no other form.  4-B staging loads: a position's run of L floats is 8-B
+// aligned only for even L.
+constexpr int NC_CK = 8;
+constexpr int NC_PL = CM_NH * CM_NT + 16;
+constexpr int NC_BOX = NC_CK * NC_PL;
+
+// A lane value the optimiser must take as new at this point.  The kernels below loop over chunks,
+// column groups or tiles around fully unrolled bodies; without it every address of the body that does
+// not depend on the loop variable is hoisted out of the loop and kept in registers (256 VGPRs, one
+// workgroup per CU; or spills at a higher occupancy).
+__device__ __forceinline__ int nc_opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// stage channels c0 .. c0 + CS - 1 (CS = 1, 2, 4 or 8: the chunk's live channels rounded up, so the
+// short last chunk of L = 9 or 10 stages one or two planes, not eight)
+template <int CS>
+__device__ __forceinline__ void nc_stage_cs(const float* __restrict__ x, int C, int c0, int hA, int wA, int hB, int wB,
+                                            int ha0, int wa0, int hb0, int wb0, long xoff, float* xa, float* xb) {
+  const int NB = hB * wB;
+  constexpr int NE = CM_NH * CM_NT * CS, IT = (NE + 255) / 256;  // loads per thread and box: 18 at CS = 8
+  const int t = nc_opaque(threadIdx.x);
+  float ra[IT], rb[IT];
+#pragma unroll
+  for (int k = 0; k < IT; ++k) {
+    const int i = t + 256 * k;
+    const int c = i % CS, p = i / CS;
+    const int bt = p % CM_NT, ah = p / CM_NT;
+    const int ha = ha0 - 1 + ah / CM_H, wa = wa0 - 1 + ah % CM_H;
+    const int hb = hb0 + bt / CM_T, wb = wb0 + bt % CM_T;
+    const bool in = i < NE && c0 + c < C && (unsigned)ha < (unsigned)hA && (unsigned)wa < (unsigned)wA && hb < hB &&
+                    wb < wB;
+    ra[k] = in ? x[xoff + (((long)(ha * wA + wa) * NB) + hb * wB + wb) * C + c0 + c] : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < IT; ++k) {
+    const int i = t + 256 * k;
+    const int c = i % CS, p = i / CS;
+    const int bh = p % CM_NH, at = p / CM_NH;
+    const int ha = ha0 + at / CM_T, wa = wa0 + at % CM_T;
+    const int hb = hb0 - 1 + bh / CM_H, wb = wb0 - 1 + bh % CM_H;
+    const bool in = i < NE && c0 + c < C && ha < hA && wa < wA && (unsigned)hb < (unsigned)hB &&
+                    (unsigned)wb < (unsigned)wB;
+    rb[k] = in ? x[xoff + (((long)(ha * wA + wa) * NB) + hb * wB + wb) * C + c0 + c] : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < IT; ++k) {
+    const int i = t + 256 * k;
+    if (i < NE) {
+      xa[(i % CS) * NC_PL + i / CS] = ra[k];
+      xb[(i % CS) * NC_PL + i / CS] = rb[k];
+    }
+  }
+}
+// nc live channels (workgroup-uniform): planes 0 .. nc - 1 are staged, the others are not read
+__device__ __forceinline__ void nc_stage(const float* __restrict__ x, int C, int c0, int nc, int hA, int wA, int hB,
+                                         int wB, int ha0, int wa0, int hb0, int wb0, long xoff, float* xa, float* xb) {
+  if (nc > 4)
+    nc_stage_cs<8>(x, C, c0, hA, wA, hB, wB, ha0, wa0, hb0, wb0, xoff, xa, xb);
+  else if (nc > 2)
+    nc_stage_cs<4>(x, C, c0, hA, wA, hB, wB, ha0, wa0, hb0, wb0, xoff, xa, xb);
+  else if (nc > 1)
+    nc_stage_cs<2>(x, C, c0, hA, wA, hB, wB, ha0, wa0, hb0, wb0, xoff, xa, xb);
+  else
+    nc_stage_cs<1>(x, C, c0, hA, wA, hB, wB, ha0, wa0, hb0, wb0, xoff, xa, xb);
+}
+// K row k of a chunk of nc channels -> (tap, channel): rows (tap, channel) dense, 9 nc of them
+__device__ __forceinline__ void nc_row(int k, int nc, int& tap, int& c) {
+  if (nc == NC_CK) {
+    tap = k >> 3, c = k & 7;
+  } else {
+    tap = k / nc, c = k - tap * nc;
+  }
+}
+
+// forward L -> 10: cp4d_mfma_kernel's groups (rows the 16 tile b positions of one tile a position,
+// columns the output channels), the accumulators carried over the chunks, bias + ReLU once at the
+// end.  K row k = 4 m + g4 of a chunk of nc live channels is (tap k / nc, channel k % nc), dense as
+// cp4d_mfma_kernel's: ceil(9 nc / 4) MFMA steps per branch, 18 for a full chunk (tap m / 2, channel
+// 4 (m & 1) + g4: the four lane groups read four planes, no bank conflict), 3 for one channel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cp4d_nc_fwd_kernel(const float* __restrict__ x, int L, int hA, int wA, int hB,
+                                                          int wB, const float* __restrict__ Wa,
+                                                          const float* __restrict__ ba, const float* __restrict__ Wb,
+                                                          const float* __restrict__ bb, float* __restrict__ y) {
+  constexpr int COUT = 10, NM = 9 * NC_CK / 4;
+  __shared__ float xa[NC_BOX];
+  __shared__ float xb[NC_BOX];
+  const int NA = hA * wA, NB = hB * wB;
+  const int ntb = (wB + CM_T - 1) / CM_T, nta = (wA + CM_T - 1) / CM_T;
+  const int ta = blockIdx.y, tb = blockIdx.x;
+  const int ha0 = (ta / nta) * CM_T, wa0 = (ta % nta) * CM_T;
+  const int hb0 = (tb / ntb) * CM_T, wb0 = (tb % ntb) * CM_T;
+  const long xoff = (long)blockIdx.z * NA * NB * L;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int r = lane & 15, g4 = lane >> 4;
+  const int by = r / CM_T, bx = r % CM_T;
+  f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < L; c0 += NC_CK) {
+    const int nc = min(NC_CK, L - c0);  // the chunk's live channels
+    const int nm = (9 * nc + 3) >> 2;   // its MFMA steps per branch
+    if (c0) __syncthreads();  // the previous chunk's LDS reads are done
+    nc_stage(x, L, c0, nc, hA, wA, hB, wB, ha0, wa0, hb0, wb0, xoff, xa, xb);
+    float wra[NM], wrb[NM];
+    int offa[NM], offb[NM];
+    const int g4 = nc_opaque(lane >> 4);
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      int tap, c;
+      nc_row(4 * m + g4, nc, tap, c);
+      const bool kin = tap < 9;  // rows past 9 nc: zero weights, a staged address
+      tap = kin ? tap : 0, c = kin ? c : 0;
+      const int ky = tap / 3, kx = tap - 3 * ky;
+      const bool live = kin && r < COUT;
+      const int wi = (r * L + c0 + c) * 9 + tap;
+      wra[m] = live ? Wa[wi] : 0.f;
+      wrb[m] = live ? Wb[wi] : 0.f;
+      offa[m] = c * NC_PL + (ky * CM_H + kx) * CM_NT + r;
+      offb[m] = c * NC_PL + (by + ky) * CM_H + bx + kx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      if (m < nm) {  // workgroup-uniform
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int G = wv * 4 + j, ay = G / CM_T, ax = G % CM_T;
+          const float va = xa[offa[m] + (ay * CM_H + ax) * CM_NT];
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(va, wra[m], acc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int G = wv * 4 + j;
+          const float vb = xb[offb[m] + G * CM_NH];
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb, wrb[m], acc[j], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // D: lane (col o = r, rows 4 g4 + i) -> pair (a = G, b = 4 g4 + i), channel o
+  if (r < COUT) {
+    const float bias = ba[r] + bb[r];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int G = wv * 4 + j;
+      const int ha = ha0 + G / CM_T, wa = wa0 + G % CM_T;
+      if (ha >= hA || wa >= wA) continue;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int bt = 4 * g4 + i;
+        const int hb = hb0 + bt / CM_T, wb = wb0 + bt % CM_T;
+        if (hb < hB && wb < wB)
+          y[(long)blockIdx.z * NA * NB * COUT + ((long)(ha * wA + wa) * NB + hb * wB + wb) * COUT + r] =
+              fmaxf(acc[j][i] + bias, 0.f);
+      }
+    }
+  }
+}
+
+// input gradient 10 -> L: cp4d_mfma_kernel<10, 1>'s tile (the 10-channel output gradient staged
+// once by cm_stage<10>, 46 KB), the L output channels walked in groups of 16 MFMA columns with the
+// group's transposed, flipped filters reloaded per group; dx accumulated when accum != 0.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cp4d_nc_dgrad_kernel(const float* __restrict__ g, int L, int hA, int wA, int hB,
+                                                            int wB, const float* __restrict__ Wa,
+                                                            const float* __restrict__ Wb, float* __restrict__ dx,
+                                                            int accum) {
+  constexpr int CIN = 10, KT = 9 * CIN, NM = (KT + 3) / 4;
+  __shared__ __attribute__((aligned(16))) float xa[CmLds<CIN>::EA + 2];
+  __shared__ __attribute__((aligned(16))) float xb[CmLds<CIN>::EB + 2];
+  const int NA = hA * wA, NB = hB * wB;
+  const int ntb = (wB + CM_T - 1) / CM_T, nta = (wA + CM_T - 1) / CM_T;
+  const int ta = blockIdx.y, tb = blockIdx.x;
+  const int ha0 = (ta / nta) * CM_T, wa0 = (ta % nta) * CM_T;
+  const int hb0 = (tb / ntb) * CM_T, wb0 = (tb % ntb) * CM_T;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int r = lane & 15, g4 = lane >> 4;
+  cm_stage<CIN>(g, hA, wA, hB, wB, ha0, wa0, hb0, wb0, (long)blockIdx.z * NA * NB * CIN, xa, xb);
+  __syncthreads();
+  for (int o0 = 0; o0 < L; o0 += 16) {
+    const int r = nc_opaque(lane & 15), g4 = nc_opaque(lane >> 4);
+    const int base_b = ((r / CM_T) * CM_H + r % CM_T) * CIN;
+    const int o = o0 + r;
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      const int k = 4 * m + g4;
+      const bool kin = k < KT;
+      const int tap = kin ? k / CIN : 0, c = kin ? k % CIN : 0;
+      const int ky = tap / 3, kx = tap - 3 * (tap / 3);
+      const bool live = kin && o < L;
+      const int wi = live ? (c * L + o) * 9 + 8 - tap : 0;
+      const float wra = live ? Wa[wi] : 0.f, wrb = live ? Wb[wi] : 0.f;
+      const int offa = (ky * CM_H + kx) * CM_NT * CIN + c, offb = (ky * CM_H + kx) * CIN + c;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int G = wv * 4 + j, ay = G / CM_T, ax = G % CM_T;
+        const float va = xa[((ay * CM_H + ax) * CM_NT + r) * CIN + offa];
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(va, wra, acc[j], 0, 0, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int G = wv * 4 + j;
+        const float vb = xb[G * CM_NH * CIN + base_b + offb];
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb, wrb, acc[j], 0, 0, 0);
+      }
+    }
+    if (o < L) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int G = wv * 4 + j;
+        const int ha = ha0 + G / CM_T, wa = wa0 + G % CM_T;
+        if (ha >= hA || wa >= wA) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int bt = 4 * g4 + i;
+          const int hb = hb0 + bt / CM_T, wb = wb0 + bt % CM_T;
+          if (hb < hB && wb < wB) {
+            float* yp = dx + (long)blockIdx.z * NA * NB * L + ((long)(ha * wA + wa) * NB + hb * wB + wb) * L + o;
+            *yp = accum ? *yp + acc[j][i] : acc[j][i];
+          }
+        }
+      }
+    }
+  }
+}
+
+// weight gradient of the L -> 10 layer: cp4d_wgrad_mfma_kernel with the (side, tap, channel) rows
+// chunked -- workgroup (g, q) keeps the 18 nc rows (nc = 8 live channels, fewer in the last chunk; rows
+// (side, tap, channel) dense: ceil(18 nc / 16) blocks of 16, 9 for a full chunk, three per wave at most)
+// of channels 8 q .. 8 q + nc - 1 in its accumulators over tiles g, g + G, ... and writes them into
+// part[g] in the same [(side, tap, o)][c] order, stride 180 L + 10, so the fixed-order
+// cp4d_wgrad_reduce_kernel sums them unchanged.  No ones row: the bias gradients are summed in
+// double by launch_cp4d_wgrad.  LDS: the two boxes and the tile's output gradient, 48,128 B.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cp4d_nc_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gm,
+                                                            int B, int L, int hA, int wA, int hB, int wB,
+                                                            float* __restrict__ part) {
+  constexpr int COUT = 10, MB = 18 * NC_CK / 16, MW = (MB + 3) / 4, NE = 18 * COUT;
+  __shared__ float xs[2 * NC_BOX];
+  __shared__ float gl[CM_NT * CM_NT][COUT];
+  float* xa = xs;
+  float* xb = xs + NC_BOX;
+  const int NA = hA * wA, NB = hB * wB;
+  const int c0 = blockIdx.y * NC_CK;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int nc = min(NC_CK, L - c0);   // live channels of this chunk
+  const int nrow = 18 * nc, mbl = (nrow + 15) >> 4;  // its rows and 16-row blocks
+  int off[MW];
+  bool inb[MW];
+#pragma unroll
+  for (int mw = 0; mw < MW; ++mw) {
+    const int kk = min(16 * (wv + 4 * mw) + i16, nrow - 1);  // rows past the last: a staged address, never written
+    int st, c;
+    nc_row(kk, nc, st, c);  // st = side * 9 + tap
+    const int side = st / 9, tap = st - 9 * side;
+    const int ky = tap / 3, kx = tap - 3 * (tap / 3);
+    inb[mw] = side != 0;
+    off[mw] = c * NC_PL + (side == 0 ? (ky * CM_H + kx) * CM_NT : NC_BOX + ky * CM_H + kx);
+  }
+  f32x4 acc[MW];
+#pragma unroll
+  for (int mw = 0; mw < MW; ++mw) acc[mw] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int ntbw = (wB + CM_T - 1) / CM_T, ntaw = (wA + CM_T - 1) / CM_T;
+  const long ntb = (long)((hB + CM_T - 1) / CM_T) * ntbw, nta = (long)((hA + CM_T - 1) / CM_T) * ntaw;
+  const long ntiles = (long)B * nta * ntb;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long tb = tile % ntb, rest = tile / ntb;
+    const long ta = rest % nta, bz = rest / nta;
+    const int ha0 = (int)(ta / ntaw) * CM_T, wa0 = (int)(ta % ntaw) * CM_T;
+    const int hb0 = (int)(tb / ntbw) * CM_T, wb0 = (int)(tb % ntbw) * CM_T;
+    __syncthreads();  // the previous tile's LDS reads are done
+    nc_stage(x, L, c0, nc, hA, wA, hB, wB, ha0, wa0, hb0, wb0, bz * NA * NB * L, xa, xb);
+    for (int e = nc_opaque(t); e < CM_NT * CM_NT * COUT; e += 256) {
+      const int o = e % COUT, p = e / COUT;
+      const int at = p / CM_NT, bt = p % CM_NT;
+      const int ha = ha0 + at / CM_T, wa = wa0 + at % CM_T, hb = hb0 + bt / CM_T, wb = wb0 + bt % CM_T;
+      const bool in = ha < hA && wa < wA && hb < hB && wb < wB;
+      (&gl[0][0])[e] = in ? gm[(bz * NA * NB + (long)(ha * wA + wa) * NB + hb * wB + wb) * COUT + o] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int st = 0; st < CM_NT * CM_NT / 4; ++st) {
+      const int p = 4 * st + g4, at = p / CM_NT, bt = p % CM_NT;
+      const int terma = ((at / CM_T) * CM_H + at % CM_T) * CM_NT + bt;
+      const int termb = at * CM_NH + (bt / CM_T) * CM_H + bt % CM_T;
+      const float bv = i16 < COUT ? gl[p][i16] : 0.f;
+#pragma unroll
+      for (int mw = 0; mw < MW; ++mw) {
+        if (wv + 4 * mw >= mbl) continue;  // wave-uniform
+        const float av = xs[(inb[mw] ? termb : terma) + off[mw]];
+        acc[mw] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[mw], 0, 0, 0);
+      }
+    }
+  }
+  // D: lane (column o = i16, rows 4 g4 + r of block m)
+  float* pw = part + (long)blockIdx.x * (NE * L + COUT);
+  if (i16 < COUT) {
+#pragma unroll
+    for (int mw = 0; mw < MW; ++mw) {
+      const int m = wv + 4 * mw;
+      if (m >= mbl) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int kk = 16 * m + 4 * g4 + r;
+        int st, c;
+        nc_row(kk, nc, st, c);
+        if (kk < nrow) pw[(st * COUT + i16) * L + c0 + c] = acc[mw][r];
+      }
+    }
+  }
+}
+
 int launch_cp4d_wgrad_mfma(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
                            int G, float* part, hipStream_t st) {
 #define CWT_WGM(CI, CO)                                                                                            \
@@ -578,7 +905,13 @@ int launch_cp4d_wgrad_mfma(const float* x, const float* gm, int B, int hA, int w
   CWT_WGM(10, 10)
   CWT_WGM(10, 1)
 #undef CWT_WGM
-  return fail(CWT_EARG, "cp4d wgrad: channels (1|2 -> 10, 10 -> 10, 10 -> 1) only");
+  if (cout == 10 && cin >= 1 && cin <= CWT_MATCH_MAX_L) {  // any other first-layer width: the chunked form
+    hipLaunchKernelGGL(cp4d_nc_wgrad_kernel, dim3(G, cdiv(cin, NC_CK)), dim3(256), 0, st, x, gm, B, cin, hA, wA, hB, wB,
+                       part);
+    CWT_LAUNCH_CHECK();
+    return 0;
+  }
+  return fail(CWT_EARG, "cp4d wgrad: channels (1..32 -> 10, 10 -> 10, 10 -> 1) only");
 }
 
 // COUT = 1 (the consensus stack's last layer, CIN = 10): a thread per (a, b) pair of the same
@@ -1890,6 +2223,15 @@ int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int
   // rest one tile per workgroup; CWT_CP4D_PERSIST=0 / 2: none / all persistent (A/B);
   // CWT_CP4D_MFMA=0 selects the scalar kernel
   static const bool mfma = !(getenv("CWT_CP4D_MFMA") && getenv("CWT_CP4D_MFMA")[0] == '0');
+  // a first layer of any other width (MMN's every-block channels), or variant 3: the channel-chunked form
+  if (variant == 3 || (cin != 1 && cin != 2 && cin != 10)) {
+    if (cout != 10 || cin < 1 || cin > CWT_MATCH_MAX_L || (variant != 0 && variant != 3))
+      return fail(CWT_EARG, "cp4d layer: the channel-chunked form takes 1..32 -> 10 channels");
+    const dim3 g4(cdiv(hB, CM_T) * cdiv(wB, CM_T), cdiv(hA, CM_T) * cdiv(wA, CM_T), B);
+    hipLaunchKernelGGL(cp4d_nc_fwd_kernel, g4, dim3(256), 0, st, x, cin, hA, wA, hB, wB, Wa, ba, Wb, bb, y);
+    CWT_LAUNCH_CHECK();
+    return 0;
+  }
   if (((mfma && variant == 0 && (cp4d_roll_mode() == 2 || (cp4d_roll_mode() == 1 && cout == 10))) || variant == 2) &&
       (cout == 10 || cout == 1) &&
       launch_cp4d_roll(x, B, hA, wA, hB, wB, cin, cout == 10 ? 0 : 2, Wa, ba, Wb, bb, y, 0, st) == 0)
@@ -1961,6 +2303,13 @@ int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int
 int launch_cp4d_dgrad(const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout, const float* Wa,
                       const float* Wb, float* dx, int accum, hipStream_t st) {
   static const bool scalar = getenv("CWT_DGRAD_SCALAR") && getenv("CWT_DGRAD_SCALAR")[0] == '1';  // A/B only
+  if (gin == 10 && gout != 1 && gout != 2 && gout != 10) {  // the L -> 10 first layer's, any other L
+    if (gout < 1 || gout > CWT_MATCH_MAX_L) return fail(CWT_EARG, "cp4d input gradient: 10 -> 1..32 channels");
+    const dim3 g4(cdiv(hB, CM_T) * cdiv(wB, CM_T), cdiv(hA, CM_T) * cdiv(wA, CM_T), B);
+    hipLaunchKernelGGL(cp4d_nc_dgrad_kernel, g4, dim3(256), 0, st, g, gout, hA, wA, hB, wB, Wa, Wb, dx, accum);
+    CWT_LAUNCH_CHECK();
+    return 0;
+  }
   if (gout == 10 && (gin == 1 || gin == 10) && !scalar) {  // 10 output channels: the matrix-core form
     if (cp4d_roll_mode() != 0 &&
         launch_cp4d_roll(g, B, hA, wA, hB, wB, gin, 1, Wa, nullptr, Wb, nullptr, dx, accum, st) == 0)
@@ -1988,7 +2337,7 @@ int launch_cp4d_dgrad(const float* g, int B, int hA, int wA, int hB, int wB, int
   CWT_CPD(10, 1)
   CWT_CPD(10, 2)
 #undef CWT_CPD
-  return fail(CWT_EARG, "cp4d input gradient: channels (1 -> 10, 10 -> 10, 10 -> 1|2) only");
+  return fail(CWT_EARG, "cp4d input gradient: channels (1 -> 10, 10 -> 10, 10 -> 1..32) only");
 }
 
 int launch_to_channels_last(const float* x, int B, int C, long P, float* y, hipStream_t st) {

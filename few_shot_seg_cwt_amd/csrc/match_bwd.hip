@@ -10,6 +10,7 @@
 // b = (hb, wb); WeightAverage's tpg [N·P][3co] = theta | phi | g before their biases.
 #include <cstdlib>
 
+#include "../../include/cwt.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -379,18 +380,24 @@ __global__ void colsum_f64_final_kernel(const double* __restrict__ part, int nch
 }
 
 // workgroups of the weight-gradient pass: 512 for the 10 -> 10 layer (two per CU by LDS), 2048 for
-// the thinner layers (less LDS each; measured 0.52 against 1.26 ms for 2 -> 10 at 60^2)
-static int wgrad_grid(int cin, int cout) { return cin * cout >= 100 ? 512 : 2048; }
+// the thinner layers (less LDS each; measured 0.52 against 1.26 ms for 2 -> 10 at 60^2); 256 per
+// channel chunk for the chunked L -> 10 form (cp4d_nc_wgrad_kernel: its partials are 180 L + 10 floats)
+static bool wgrad_chunked(int cin, int cout) { return cout == 10 && cin != 1 && cin != 2 && cin != 10; }
+static int wgrad_grid(int cin, int cout) { return wgrad_chunked(cin, cout) ? 256 : cin * cout >= 100 ? 512 : 2048; }
 int cp4d_wgrad_part_floats(int cin, int cout) {
   (void)cin;
   (void)cout;
-  return std::max(512 * (18 * 10 * 10 + 10), 2048 * (18 * 10 * 2 + 10));  // the largest of the four layers
+  // the largest of the layers, the chunked form at CWT_MATCH_MAX_L included
+  return std::max(std::max(512 * (18 * 10 * 10 + 10), 2048 * (18 * 10 * 2 + 10)), 256 * (18 * 10 * CWT_MATCH_MAX_L + 10));
 }
 
 int launch_cp4d_wgrad(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
                       float* part, size_t part_floats, float* dWa, float* dWb, float* db1, float* db2,
                       hipStream_t st) {
-  const long ntiles = (long)B * cdiv(hA, WG_TAH) * cdiv(wA, WG_TAW) * cdiv(hB, WG_TBH) * cdiv(wB, WG_TBW);
+  // the chunked form walks the matrix-core kernels' 4 x 4 by 4 x 4 tiles: its grid is sized by their count
+  const long ntiles = wgrad_chunked(cin, cout)
+                          ? (long)B * cdiv(hA, 4) * cdiv(wA, 4) * cdiv(hB, 4) * cdiv(wB, 4)
+                          : (long)B * cdiv(hA, WG_TAH) * cdiv(wA, WG_TAW) * cdiv(hB, WG_TBH) * cdiv(wB, WG_TBW);
   const int G = (int)std::min<long>(wgrad_grid(cin, cout), ntiles);
   const int n = 18 * cout * cin + cout;
   if ((size_t)G * n > part_floats) return fail(CWT_ESTATE, "cp4d wgrad: partial workspace too small");

@@ -20,8 +20,9 @@ The reference's DeTr.compute_feat (detr.py:49-61) indexes ``fq_lst[int(l) - 2]``
 the entries, which does not match what this repo's reference PSPNet.get_feat_list returns (a dict
 {2, 3, 4: [feature]}, pspnet.py:272-287): as written it cannot run against that extractor.  Here
 ``rmid`` names the layers as in_fea_dim_lookup does ('l34' = layer3 + layer4, 1024 + 2048
-channels, detr.py:10), and fq_lst / fs_lst may be that dict (of features or one-element lists) or
-a list indexed by layer - 2.
+channels, detr.py:10), and fq_lst / fs_lst may be that dict (of features or of lists: DeTr reads one
+feature per layer, the list's last entry -- the layer's last block, also where all_lr makes the
+extractor return every block) or a list indexed by layer - 2.
 
 Training (round 4): under autograd every op of the head has its device
 backward -- cwt_linear_backward (adjust_feature's segments, the four MSDeformAttn projections),
@@ -400,7 +401,8 @@ class DeTr(torch.nn.Module):
             f = lst[lid]
         else:
             f = lst[lid - 2]
-        return f[0] if isinstance(f, (list, tuple)) else f
+        # one feature per layer: the last block (with all_lr naming the layer the list holds every block)
+        return f[-1] if isinstance(f, (list, tuple)) else f
 
     def _adjust(self, feats):
         """relu(sum_l x_l . W_l^T) over the layer segments (the concatenation never materialised)."""

@@ -25,11 +25,13 @@ encoder's weight / bias gradients (train_match.py:104 sce=args.sce).
 The modules keep the reference's parameter names (``NeighConsensus.conv.{0,2,4}.conv{1,2}.
 {weight,bias}``), so a reference state_dict loads as is.  Built: the default head of every MMN /
 MatchNet script -- CenterPivotConv4d ('red'), kernel sizes [3, 3, 3], channels [10, 10, 1],
-in_channel 1 or 2, symmetric or not -- and the MMN head of the mmn configs (rmid 'l34', all_lr
-'l', agg 'cat', wa True, red_dim False), forward only (inference), with MatchNet.forward's ig_mask and (round 3) its
+in_channel 1 .. 32 (1 or 2 on the kernels instantiated for them, any other width on the
+channel-chunked first layer), symmetric or not -- and the MMN head of the mmn configs (rmid
+'l34' / 'l234', all_lr 'l' or naming layers: one correlation channel per (layer, bottleneck) pair,
+mmn.py:39; agg 'cat', wa True, red_dim False), with MatchNet.forward's ig_mask and (round 3) its
 cycle-consistency mask (cyc; training mode since round 5), and NeighConsensus over full Conv4d layers ('cv4',
 fp32 VALU), the spatial context encoder (sce, spatial_context.py), and MMN's agg 'sum' and red_dim.
-Not built: forward_mmn (its MSBlock) and the MMN trainers' backward.
+Not built: forward_mmn (its MSBlock).
 
 Parity is unpinned: the reference cannot be run here and holds no fixtures for
 this head; tests/test_gpu_match.py checks it against oracle/match_oracle.py, a float64
@@ -47,6 +49,8 @@ from . import _lib
 from .heads import get_corr
 from .transformer import as_tokens
 from .util import dropout_seed
+
+MATCH_MAX_L = 32   # CWT_MATCH_MAX_L (include/cwt.h): the widest correlation of the 'red' consensus stack
 
 
 def MutualMatching(corr4d: torch.Tensor) -> torch.Tensor:
@@ -106,8 +110,10 @@ class NeighConsensus(torch.nn.Module):
         if conv not in ("red", "cv4"):
             raise ValueError(f"NeighConsensus: conv must be 'red' or 'cv4' (match.py:15), got {conv!r}")
         self.conv_type = conv
-        if tuple(kernel_sizes) != (3, 3, 3) or tuple(channels) != (10, 10, 1) or in_channel not in (1, 2):
-            raise NotImplementedError("NeighConsensus: kernel sizes [3,3,3], channels [10,10,1], in_channel 1 or 2")
+        max_in = MATCH_MAX_L if conv == "red" else 2   # CWT_MATCH_MAX_L (include/cwt.h); Conv4d layers: 1 or 2
+        if tuple(kernel_sizes) != (3, 3, 3) or tuple(channels) != (10, 10, 1) or not 1 <= int(in_channel) <= max_in:
+            raise NotImplementedError("NeighConsensus: kernel sizes [3,3,3], channels [10,10,1], in_channel 1..32 "
+                                      "('red') or 1..2 ('cv4')")
         self.symmetric_mode = symmetric_mode
         self.kernel_sizes = list(kernel_sizes)
         self.channels = list(channels)
@@ -772,8 +778,6 @@ class MMN(torch.nn.Module):
         self.nbottlenecks = [3, 4, 6, 3] if layers == 50 else [3, 4, 23, 3]
         self.feature_channels = [256, 512, 1024, 2048]
         all_lr = str(_get(args, "all_lr", "l"))
-        if any(str(i) in all_lr for i in self.bid_lst):
-            raise NotImplementedError("MMN: every-bottleneck features (all_lr naming a layer) are not built")
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         if wa or red_dim:   # mmn.py:26-33: the wa_ modules exist whenever red_dim does
             for bid in self.bid_lst:
@@ -784,7 +788,10 @@ class MMN(torch.nn.Module):
                                                 torch.nn.ReLU(inplace=True)))
                     c_in = red_dim
                 setattr(self, "wa_" + str(bid), WeightAverage(c_in, args, device=dev))
-        match_ch = 1 if agg == "sum" else len(self.bid_lst)
+        # mmn.py:36-39: one channel per (layer, bottleneck) pair -- every bottleneck of a layer named in
+        # all_lr, the last one of the others; the wa_ / rd_ modules stay one per layer
+        match_ch = 1 if agg == "sum" else sum(self.nbottlenecks[i - 1] if str(i) in all_lr else 1
+                                              for i in self.bid_lst)
         self.att_wt = float(_get(args, "att_wt", 0.2))
         self.corr_net = MatchNet(temp=float(_get(args, "temp", 20.0)), cv_type=str(_get(args, "conv4d", "red")),
                                  sce=False, cyc=False, sym_mode=True, in_channel=match_ch, device=dev)
@@ -802,34 +809,37 @@ class MMN(torch.nn.Module):
         """forward under autograd: red_dim's 1x1 conv + ReLU, WeightAverage, the stacked (or, agg
         'sum', summed) correlations, corr_forward and the blend as differentiable device ops."""
         B, ch, h, w = f_s.shape
-        L = len(self.bid_lst)
         feats = []
-        for idx in self.bid_lst[::-1]:
-            fq_fea, fs_fea = fq_lst[idx][0], fs_lst[idx][0]
-            if self.red_dim:
-                fq_fea, fs_fea = self._reduce(idx, fq_fea), self._reduce(idx, fs_fea)
-            if self.wa:
-                m = getattr(self, "wa_" + str(idx))
-                fq_fea, fs_fea = m(fq_fea), m(fs_fea)
-            feats += [as_tokens(fq_fea), as_tokens(fs_fea)]
+        for idx in self.bid_lst[::-1]:   # mmn.py:46-47: the deepest layer first, its blocks ascending
+            for lr in range(len(fq_lst[idx])):
+                fq_fea, fs_fea = fq_lst[idx][lr], fs_lst[idx][lr]
+                if self.red_dim:
+                    fq_fea, fs_fea = self._reduce(idx, fq_fea), self._reduce(idx, fs_fea)
+                if self.wa:   # one module per layer: its parameters' gradients accumulate over the blocks
+                    m = getattr(self, "wa_" + str(idx))
+                    fq_fea, fs_fea = m(fq_fea), m(fs_fea)
+                feats += [as_tokens(fq_fea), as_tokens(fs_fea)]
+        L = len(feats) // 2
         corr4d = _MMNCorrFn.apply(B, L, self.agg == "sum", *feats)
         attn, att = self.corr_net._run(corr4d, h, w, f_s)
         fq, att_fq = _MMNBlendFn.apply(as_tokens(f_q), as_tokens(att), self.att_wt)
         return (attn, fq, att_fq) if ret_attn else (fq, att_fq)
 
     def forward(self, fq_lst, fs_lst, f_q, f_s, ret_attn: bool = False):
-        """mmn.py:42-71: fq_lst / fs_lst {layer: [feature]} (extract_features with rmid),
+        """mmn.py:42-71: fq_lst / fs_lst {layer: [feature, ...]} (extract_features with rmid: every
+        bottleneck's feature of a layer named in all_lr, else the last one's),
         f_q [1, C, h, w], f_s [B, C, h, w] -> (fq, att_fq) [or (attn, fq, att_fq)].  Under
         autograd (a parameter or an input requiring grad) the backward runs on the device."""
-        feats_in = [t for lst in (fq_lst, fs_lst) for idx in self.bid_lst for t in lst[idx][:1]]
+        feats_in = [t for lst in (fq_lst, fs_lst) for idx in self.bid_lst for t in lst[idx]]
         if _needs_grad(f_q, f_s, *feats_in, *self.parameters()):
             return self._forward_train(fq_lst, fs_lst, f_q, f_s, ret_attn)
         B, ch, h, w = f_s.shape
         P = h * w
-        L = len(self.bid_lst)
+        pairs = [(idx, lr) for idx in self.bid_lst[::-1] for lr in range(len(fq_lst[idx]))]   # mmn.py:46-47
+        L = len(pairs)
         corr4d = torch.empty((B, L, P, P), device=f_s.device, dtype=torch.float32)
-        for li, idx in enumerate(self.bid_lst[::-1]):
-            fq_fea, fs_fea = fq_lst[idx][0], fs_lst[idx][0]
+        for li, (idx, lr) in enumerate(pairs):
+            fq_fea, fs_fea = fq_lst[idx][lr], fs_lst[idx][lr]
             if self.red_dim:   # rd_<layer>: 1x1 conv (no bias) + ReLU on the device GEMM
                 fq_fea, fs_fea = self._reduce(idx, fq_fea), self._reduce(idx, fs_fea)
             if self.wa:

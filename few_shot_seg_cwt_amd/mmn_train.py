@@ -15,7 +15,7 @@ Order of operations per training episode (train_kshot.py:128-192):
 Host readback happens only where the reference prints or fills its meters.
 
 Declared differences: use_amp (fp16 autocast + GradScaler) is not reproduced, the step runs at
-fp32 width; all_lr naming a layer raises (MMN); meta_aug stays out; under WeightAverage's
+fp32 width; meta_aug stays out; under WeightAverage's
 dropouts the query feature is averaged once per MMN call, not once per expanded support row.
 """
 from __future__ import annotations

@@ -70,13 +70,12 @@ class PSPNet:
         if self.conv_dtype not in self._PRECISION:
             raise ValueError(f"conv_dtype must be one of {sorted(self._PRECISION)}")
         # per-layer features for the MMN / MatchNet variants (pspnet.py:172-181): returned when
-        # rmid names layers ('l34', 'mid3', ...); get_feat_list keeps each layer's last block
-        # (all_lr 'l'; every block of a named layer is not built)
+        # rmid names layers ('l34', 'mid3', ...); get_feat_list (pspnet.py:272-287) keeps every
+        # bottleneck's output of a layer whose digit is in all_lr, the last block of the others
         self.rmid = _arg(args, "rmid", None)
         self.all_lr = str(_arg(args, "all_lr", "l"))
         self.mid_features = self.rmid is not None and ("l" in str(self.rmid) or "mid" in str(self.rmid))
-        if self.mid_features and any(ch.isdigit() for ch in self.all_lr):
-            raise NotImplementedError("all_lr naming layers (every bottleneck's features) is not built")
+        self.nbottlenecks = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}[self.layers]
 
     _PRECISION = {"fp32": 0, "bf16": 1}  # CWT_CONV_FP32 / CWT_CONV_BF16 (include/cwt.h)
 
@@ -178,7 +177,8 @@ class PSPNet:
     # -- hot path ------------------------------------------------------------------------
     def extract_features(self, x: torch.Tensor, out: torch.Tensor | None = None):
         """pspnet.py:172-181: returns (f [N,512,h,w] channels_last, []), or with an rmid naming
-        layers (f, {2: [layer2], 3: [layer3], 4: [layer4]}) (channels_last, fp32)."""
+        layers (f, {2: [...], 3: [...], 4: [...]}) (channels_last, fp32): per layer every bottleneck's
+        output in block order if the layer's digit is in all_lr, else its last block's alone."""
         if self._state is None:
             raise RuntimeError("load_state_dict first")
         _lib.require(x, "x")
@@ -203,12 +203,23 @@ class PSPNet:
             self._stats_moved = True
             return out, []
         if self.mid_features:
-            mids = {lid: torch.empty((N, c, h, h), device=x.device, dtype=torch.float32,
-                                     memory_format=torch.channels_last) for lid, c in ((2, 512), (3, 1024), (4, 2048))}
-            _lib.check(_lib.lib().cwt_extract_features_mid(
-                _lib.ctx(x.device.index), self._handle, _lib.ptr(x), N, S, _lib.ptr(out), _lib.ptr(mids[2]),
-                _lib.ptr(mids[3]), _lib.ptr(mids[4]), _lib.stream_ptr(x.device)), "cwt_extract_features_mid")
-            return out, {lid: [t] for lid, t in mids.items()}
+            req = []   # (layer, block) in network order
+            for lid in (2, 3, 4):
+                nb = self.nbottlenecks[lid - 1]
+                req += [(lid, b) for b in (range(nb) if str(lid) in self.all_lr else (nb - 1,))]
+            chans = {2: 512, 3: 1024, 4: 2048}
+            outs = [torch.empty((N, chans[lid], h, h), device=x.device, dtype=torch.float32,
+                                memory_format=torch.channels_last) for lid, _ in req]
+            n = len(req)
+            _lib.check(_lib.lib().cwt_extract_features_blocks(
+                _lib.ctx(x.device.index), self._handle, _lib.ptr(x), N, S, _lib.ptr(out), n,
+                (C.c_int * n)(*[lid for lid, _ in req]), (C.c_int * n)(*[b for _, b in req]),
+                (C.c_void_p * n)(*[t.data_ptr() for t in outs]), _lib.stream_ptr(x.device)),
+                "cwt_extract_features_blocks")
+            feats = {2: [], 3: [], 4: []}
+            for (lid, _), t in zip(req, outs):
+                feats[lid].append(t)
+            return out, feats
         _lib.check(_lib.lib().cwt_extract_features(_lib.ctx(x.device.index), self._handle, _lib.ptr(x), N, S,
                                                    _lib.ptr(out),
                                                    _lib.stream_ptr(x.device)), "cwt_extract_features")

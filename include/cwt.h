@@ -118,6 +118,17 @@ int cwt_extract_features(cwt_ctx* ctx, const cwt_backbone* bb, const float* img,
 int cwt_extract_features_mid(cwt_ctx* ctx, const cwt_backbone* bb, const float* img, int N, int S, float* feat,
                              float* l2, float* l3, float* l4, void* stream);
 
+/* extract_features with the outputs of chosen bottlenecks (get_feat_list pspnet.py:272-287 with
+ * all_lr naming layers: every bottleneck of a named layer, the last one of the others): as
+ * cwt_extract_features, plus n_out fp32 NHWC copies.  Entry i is the output (after the residual
+ * and ReLU) of bottleneck block[i] (0-based) of layer[i] in {2, 3, 4}, block[i] below the
+ * layer's count (4 / 6 / 3 for 50 layers, 4 / 23 / 3 for 101), written to out[i] device
+ * [N][h][h][512 / 1024 / 2048] (h = the feature side); layer, block and out are host arrays, a
+ * (layer, block) pair named twice is CWT_EARG.  Requests for the last blocks only run the plan of
+ * cwt_extract_features_mid, no request (n_out 0) that of cwt_extract_features.  Eval-mode BN. */
+int cwt_extract_features_blocks(cwt_ctx* ctx, const cwt_backbone* bb, const float* img, int N, int S, float* feat,
+                                int n_out, const int* layer, const int* block, float* const* out, void* stream);
+
 int cwt_extract_features_train_bn(cwt_ctx* ctx, cwt_backbone* bb, const float* img, int N, int S,
                                   float* feat, float momentum, float dropout_p, uint64_t seed,
                                   void* stream);
@@ -397,9 +408,16 @@ int cwt_corr(cwt_ctx* ctx, const float* q, const float* k, int B, int Pq, int Pk
  * C <= 64. */
 int cwt_mutual_matching(cwt_ctx* ctx, const float* x, int B, int NA, int NB, int C, float* y, void* stream);
 
+/* The widest correlation (in_channel) of the cwt_match_corr_* entries with CenterPivotConv4d
+ * layers: MMN's one channel per (layer, bottleneck) pair (src/model/mmn.py:39) is 30 at most
+ * (101 layers, rmid l234, all_lr 234). */
+#define CWT_MATCH_MAX_L 32
+
 /* MatchNet.corr_forward (src/model/match.py:142-163; NeighConsensus :56-85 with the default
  * kernel sizes [3,3,3], channels [10,10,1] and CenterPivotConv4d layers, conv4d.py:11-62):
- * corr device [B][L][h*w][h*w] (the torch [B, L, h, w, h, w] tensor, L = in_channel 1 or 2);
+ * corr device [B][L][h*w][h*w] (the torch [B, L, h, w, h, w] tensor, L = in_channel,
+ * 1 <= L <= CWT_MATCH_MAX_L; L = 1, 2 run the kernels instantiated for them, any other L the
+ * channel-chunked first layer);
  * nc_params device: per layer l = 0, 1, 2 (channels L -> 10 -> 10 -> 1) conv1.weight [co][ci][3][3],
  * conv1.bias [co], conv2.weight [co][ci][3][3], conv2.bias [co], concatenated (the order of
  * NeighConsensus.conv.{0,2,4}.{conv1,conv2}.{weight,bias} in its state_dict); symmetric = the
@@ -414,7 +432,8 @@ int cwt_match_corr_forward(cwt_ctx* ctx, const float* corr, int B, int L, int h,
 /* cwt_match_corr_forward with NeighConsensus over full Conv4d layers (conv='cv4', src/model/
  * conv4d.py:64-138; match.py:15,56-85): nc_params device = per layer (0, 2, 4) the reference's
  * pre-permuted weight [3][co][ci][3][3][3] then its bias [co].  fp32 VALU (no MFMA path: every
- * reference config uses 'red'). */
+ * reference config uses 'red'), forward only and used by no trainer, so it stays at L = 1 or 2:
+ * CWT_EARG for a wider correlation. */
 int cwt_match_corr_forward_cv4(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
                                int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
                                void* stream);
@@ -496,11 +515,13 @@ int cwt_adapt_fuses_tail(cwt_ctx* ctx, int n, int h, int w, int iters, int* fuse
 
 /* Floats of the activations cwt_match_corr_forward_train keeps for the backward (CenterPivotConv4d
  * layers): the MutualMatching output, each branch's three ReLU outputs, their sum and, with
- * readout != 0, the attention [B][h*w][ld] (ld = h*w rounded up to 32). */
+ * readout != 0, the attention [B][h*w][ld] (ld = h*w rounded up to 32).  1 <= L <= CWT_MATCH_MAX_L,
+ * CWT_EARG otherwise. */
 int cwt_match_corr_saved_floats(int B, int L, int h, int w, int symmetric, int readout, int64_t* n);
 
 /* cwt_match_corr_forward (match.py:142-163, 'red' layers) keeping its activations in saved
- * device [cwt_match_corr_saved_floats]: the forward of MatchNet.corr_forward under autograd. */
+ * device [cwt_match_corr_saved_floats]: the forward of MatchNet.corr_forward under autograd
+ * (1 <= L <= CWT_MATCH_MAX_L, as the backward). */
 int cwt_match_corr_forward_train(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w,
                                  const float* nc_params, int symmetric, float temp, const float* v, int Cv,
                                  float* corr2d, float* weighted_v, float* saved, void* stream);
@@ -509,7 +530,8 @@ int cwt_match_corr_forward_train(cwt_ctx* ctx, const float* corr, int B, int L, 
  * device [B][h*w][Cv] (at weighted_v, or NULL) -> d_corr device [B][L][h*w][h*w] (or NULL), d_params
  * device (nc_params' layout: every conv1 / conv2 weight and bias of the three layers, both branches
  * summed), d_v device [B][h*w][Cv] (or NULL).  MutualMatching's maxima route their gradient to the
- * first maximal position (torch.max's single index); Cv % 4 == 0. */
+ * first maximal position (torch.max's single index) per channel; Cv % 4 == 0.  Every sum runs in a
+ * fixed order: two calls on the same inputs give the same bits, for every L. */
 int cwt_match_corr_backward(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
                             int symmetric, float temp, const float* v, int Cv, const float* saved,
                             const float* d_corr2d, const float* d_weighted_v, float* d_corr, float* d_params,

@@ -147,7 +147,8 @@ int cwt_debug_splitk_epilogue(cwt_ctx* ctx, const float* part, int nsplit, int M
 /* One CenterPivotConv4d layer + ReLU (src/model/conv4d.py:40-62) on the channels-last 4-D
  * tensor x [B][hA*wA][hB*wB][cin] -> y [B][hA*wA][hB*wB][cout]: Wa / Wb [cout][cin][3][3] the
  * a-plane / b-plane filters, ba / bb their biases.  variant 0: the library's kernel choice, 1:
- * never the rolling-window kernel (cp4d_roll_kernel), 2: only it (CWT_EARG where it has no form). */
+ * never the rolling-window kernel (cp4d_roll_kernel), 2: only it (CWT_EARG where it has no form),
+ * 3: the channel-chunked kernel of the wide first layer (cp4d_nc_fwd_kernel; cin 1..32, cout 10). */
 int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
                          const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
                          void* stream);

@@ -1,5 +1,6 @@
 """Time one CenterPivotConv4d layer at the MMN geometry (60^2 x 60^2) per kernel variant
-(cwt_debug_cp4d_layer: 1 the tile kernels, 2 the rolling-window kernel).  CWT_CP4D_WC sets the
+(cwt_debug_cp4d_layer: 1 the tile kernels, 2 the rolling-window kernel, 3 -- for 10 output channels --
+the channel-chunked kernel of the wide first layer, on the same input).  CWT_CP4D_WC sets the
 rolling kernel's a columns per workgroup.  python tools/time_cp4d.py [reps]"""
 import json
 import os
@@ -20,7 +21,7 @@ for cin, cout in ((2, 10), (10, 10), (10, 1)):
     y = torch.empty(1, h * h, h * h, cout, device=dev)
     Wa, Wb = torch.rand(cout, cin, 3, 3, device=dev) * 0.1, torch.rand(cout, cin, 3, 3, device=dev) * 0.1
     ba, bb = torch.zeros(cout, device=dev), torch.zeros(cout, device=dev)
-    for v in (1, 2):
+    for v in (1, 2) + ((3,) if cout == 10 else ()):
         fn = lambda: _lib.check(_lib.lib().cwt_debug_cp4d_layer(  # noqa: E731
             _lib.ctx(0), _lib.ptr(x), 1, h, h, h, h, cin, cout, _lib.ptr(Wa), _lib.ptr(ba), _lib.ptr(Wb), _lib.ptr(bb),
             _lib.ptr(y), v, _lib.stream_ptr(dev)), "cwt_debug_cp4d_layer")
