@@ -463,7 +463,9 @@ int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h
 int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int64_t n, int num_classes,
                   int ignore_index, float* iut_out, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(preds && target && iut_out && n >= 0 && num_classes >= 1 && num_classes <= 16, "bad arguments");
+  // n == 0: an empty tensor has no storage (null pointers), and the kernel reads nothing
+  CWT_CHECK(((preds && target) || n == 0) && iut_out && n >= 0 && num_classes >= 1 && num_classes <= 16,
+            "bad arguments");
   CWT_HIP(hipSetDevice(ctx->device));
   unsigned* cnt;
   int rc;

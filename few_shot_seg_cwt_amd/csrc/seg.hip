@@ -348,13 +348,17 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
 
 int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom, float wd, int nesterov, int first,
                hipStream_t st) {
+  if (n == 0) return 0;  // nothing to step: an empty grid would be a launch error
   int blocks = (int)std::min<long>(2048, cdiv(n, 256));
   hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, st, p, g, buf, n, lr, mom, wd, nesterov, first);
   CWT_LAUNCH_CHECK();
   return 0;
 }
 
-// intersectionAndUnionGPU on argmax maps: counts[0..K) inter, [K..2K) output, [2K..3K) target
+// intersectionAndUnionGPU on argmax maps: counts[0..K) inter, [K..2K) output, [2K..3K) target.
+// The reference writes ignore_index into the predictions wherever the target has it
+// (util.py:301), so with an ignore index below K an ignored pixel counts as intersection, output
+// and target of that class; with one outside [0, K) (255) it counts nowhere.
 __global__ void iou_preds_kernel(const int64_t* __restrict__ preds, const int64_t* __restrict__ target, long n, int K,
                                  int ignore, unsigned* __restrict__ counts) {
   __shared__ unsigned c[48];
@@ -362,7 +366,14 @@ __global__ void iou_preds_kernel(const int64_t* __restrict__ preds, const int64_
   __syncthreads();
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int64_t t = target[i];
-    if (t == ignore) continue;
+    if (t == ignore) {
+      if (ignore >= 0 && ignore < K) {
+        atomicAdd(&c[ignore], 1u);
+        atomicAdd(&c[K + ignore], 1u);
+        atomicAdd(&c[2 * K + ignore], 1u);
+      }
+      continue;
+    }
     const int64_t p = preds[i];
     if (p >= 0 && p < K) {
       atomicAdd(&c[K + (int)p], 1u);

@@ -52,7 +52,10 @@ def dropout_seed() -> int:
 
 def intersectionAndUnionGPU(preds: torch.Tensor, target: torch.Tensor, num_classes: int,
                             ignore_index: int = 255) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """util.py:280-308 on argmax maps: returns (intersection, union, target) [num_classes] float."""
+    """util.py:280-308 on argmax maps: returns (intersection, union, target) [num_classes] float.
+    As there, a pixel whose target is ignore_index takes it as its prediction too: it counts
+    nowhere when ignore_index lies outside [0, num_classes) and as that class when inside.
+    Empty tensors give zeros."""
     assert preds.dim() in (1, 2, 3)
     assert preds.shape == target.shape
     _lib.require(preds, "preds", torch.int64)

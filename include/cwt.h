@@ -363,7 +363,10 @@ int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h
                       float* d_f, void* stream);
 
 /* intersectionAndUnionGPU on argmax maps (util.py:280-308): preds/target device int64 [n];
- * preds[target==ignore] are ignored; histc over classes 0..num_classes-1 (num_classes <= 16).
+ * preds[target==ignore] take the ignore index, as in the reference: with ignore_index outside
+ * [0, num_classes) those pixels count nowhere, with one inside they count as intersection,
+ * output and target of that class; histc over classes 0..num_classes-1 (num_classes <= 16).
+ * n == 0 (null preds / target allowed) gives zeros.
  * iut_out: device fp32 [3, num_classes] (intersection, union, target). */
 int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int64_t n, int num_classes,
                   int ignore_index, float* iut_out, void* stream);
@@ -641,7 +644,8 @@ int cwt_norm_blend(cwt_ctx* ctx, const float* a, const float* b, int64_t T, int 
 
 /* torch.optim.SGD(momentum, dampening 0, weight_decay, nesterov) step over one flat
  * fp32 parameter buffer (optimizer.py:8-15): buf = m*buf + (g + wd*p) (buf = g+wd*p on
- * the first step, first_step != 0); p -= lr * (nesterov ? g + wd*p + m*buf : buf). */
+ * the first step, first_step != 0); p -= lr * (nesterov ? g + wd*p + m*buf : buf).
+ * n == 0 is a no-op. */
 int cwt_sgd_step(cwt_ctx* ctx, float* param, const float* grad, float* momentum_buf, int64_t n,
                  float lr, float momentum, float weight_decay, int nesterov, int first_step,
                  void* stream);
