@@ -89,10 +89,14 @@ int launch_rowdot(const float* A, int R, int K, const float* X, int nv, long xvs
 // out[g][v][k] += alpha * sum_{d in chunk} A[g*Dg + d][k] * X[v*xvs + g*Dg + d]
 // (transposed GEMV per group g).  Block = (k block of 256, group, d chunk of 16); the
 // chunk's 16 rows are loaded before any FMA (16 loads in flight per lane).
+// T = double (the forward's r): the Dg / 16 workgroup partials of an element meet in a float64
+// atomic, so the sum rounded to fp32 does not depend on the order they arrive in (in fp32 that
+// order moves a peaked softmax's output by 1e-6 from run to run).
 constexpr int COLDOT_D = 16;
+template <class T>
 __global__ __launch_bounds__(64) void coldot_kernel(const float* __restrict__ A, int K, int Dg,
                                                     const float* __restrict__ X, int nv, long xvs,
-                                                    float* __restrict__ out, float alpha) {
+                                                    T* __restrict__ out, float alpha) {
   const int k = blockIdx.x * 256 + threadIdx.x * 4;
   const int g = blockIdx.y;
   const int d0 = blockIdx.z * COLDOT_D;
@@ -115,17 +119,18 @@ __global__ __launch_bounds__(64) void coldot_kernel(const float* __restrict__ A,
 #pragma unroll
   for (int v = 0; v < 8; ++v)
     if (v < nv) {
-      float* o = out + ((long)g * nv + v) * K + k;
+      T* o = out + ((long)g * nv + v) * K + k;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) atomicAdd(o + q, alpha * acc[v][q]);
+      for (int q = 0; q < 4; ++q) atomicAdd(o + q, (T)(alpha * acc[v][q]));
     }
 }
 
-int launch_coldot(const float* A, int G, int Dg, int K, const float* X, int nv, long xvs, float* out, float alpha,
+template <class T>
+int launch_coldot(const float* A, int G, int Dg, int K, const float* X, int nv, long xvs, T* out, float alpha,
                   hipStream_t st) {
   if (nv > 8) return fail(CWT_EARG, "coldot: at most 8 vectors");
   dim3 grid(cdiv(K, 256), G, cdiv(Dg, COLDOT_D));
-  hipLaunchKernelGGL(coldot_kernel, grid, dim3(64), 0, st, A, K, Dg, X, nv, xvs, out, alpha);
+  hipLaunchKernelGGL((coldot_kernel<T>), grid, dim3(64), 0, st, A, K, Dg, X, nv, xvs, out, alpha);
   CWT_LAUNCH_CHECK();
   return 0;
 }
@@ -134,14 +139,15 @@ int launch_coldot(const float* A, int G, int Dg, int K, const float* X, int nv, 
 constexpr int ATT_TPW = 8;                 // tokens per wave
 constexpr int ATT_TPB = 4 * ATT_TPW;       // tokens per workgroup
 
-// r: [H][nv][C] scores queries (already / sqrt(C)), row rho = h*2 + i of batch b is r[h][b*2+i].
+// r: [H][nv][C] scores queries (already / sqrt(C); float64 sums of coldot, rounded to fp32 here),
+// row rho = h*2 + i of batch b is r[h][b*2+i].
 // f: [B][hw][C].  part_g: [B][nchunk][NR][C]; part_ml: [B][nchunk][NR][2].
 // Optionally stores the raw scores for the backward pass: scores [B][NR][hw].
 // Training-mode attention dropout (transformer.py:17,28: dropout AFTER the softmax): token p of
 // row rho enters g with weight m = dropout_scale(p_drop, seed, 1, (b*NR + rho)*hw + p); the
 // softmax denominator l is unaffected.
 template <int NR>
-__global__ __launch_bounds__(256) void attn_partial_kernel(const float* __restrict__ r, const float* __restrict__ f,
+__global__ __launch_bounds__(256) void attn_partial_kernel(const double* __restrict__ r, const float* __restrict__ f,
                                                            int hw, int nv, float* __restrict__ part_g,
                                                            float* __restrict__ part_ml, float* __restrict__ scores,
                                                            float p_drop, unsigned long long seed) {
@@ -154,7 +160,7 @@ __global__ __launch_bounds__(256) void attn_partial_kernel(const float* __restri
   for (int i = t; i < NR * C; i += 256) {
     const int rho = i / C, k = i % C;
     const int h = rho >> 1, qi = rho & 1;
-    rs[rho][k] = r[((long)h * nv + b * 2 + qi) * C + k];
+    rs[rho][k] = (float)r[((long)h * nv + b * 2 + qi) * C + k];
   }
   __syncthreads();
   const int tok0 = chunk * ATT_TPB + wv * ATT_TPW;
@@ -538,18 +544,19 @@ __global__ void layernorm_kernel(const float* __restrict__ y, const float* __res
 
 // ---------------------------------------------------------------------------------------
 // Saved-tensor layout for the backward pass (floats), nv = 2B, NR = 2H:
-//   qp[nv][H*C] | r[H][nv][C] | g[H][nv][C] | o[nv][H*C] | y[nv][C] | ln[nv][2] |
-//   ml[B][NR][2] | scores[B][NR][hw]
+//   qp[nv][H*C] | g[H][nv][C] | o[nv][H*C] | y[nv][C] | ln[nv][2] | ml[B][NR][2] |
+//   scores[B][NR][hw]
+// (every section an even number of floats).  The forward's workspace is the same layout (when
+// nothing is saved), the chunk partials, then r[H][nv][C] in float64.
 // ---------------------------------------------------------------------------------------
 struct SavedLayout {
-  long qp, r, g, o, y, ln, ml, sc, total;
+  long qp, g, o, y, ln, ml, sc, total;
 };
 static SavedLayout saved_layout(int B, int hw, int C, int H) {
   SavedLayout L;
   const long nv = 2L * B, NR = 2L * H;
   long off = 0;
   L.qp = off; off += nv * H * C;
-  L.r = off; off += (long)H * nv * C;
   L.g = off; off += (long)H * nv * C;
   L.o = off; off += nv * H * C;
   L.y = off; off += nv * C;
@@ -563,7 +570,7 @@ size_t attention_saved_floats(int B, int hw, int C, int H) { return (size_t)save
 
 size_t attention_ws_floats(int B, int hw, int C, int H) {
   const int nchunk = cdiv(hw, ATT_TPB);
-  return (size_t)saved_layout(B, hw, C, H).total + (size_t)B * nchunk * 2 * H * (C + 2);
+  return (size_t)saved_layout(B, hw, C, H).total + (size_t)B * nchunk * 2 * H * (C + 2) + 2 * (size_t)H * 2 * B * C;
 }
 
 int attention_fwd(const float* q, const float* f, int B, int hw, int C, int H, const float* w_qkvs,
@@ -579,25 +586,26 @@ int attention_fwd(const float* q, const float* f, int B, int hw, int C, int H, c
   const int nchunk = cdiv(hw, ATT_TPB);
   float* part_g = part;
   float* part_ml = part + (long)B * nchunk * NR * C;
+  double* r = (double*)(part_ml + (long)B * nchunk * NR * 2);  // an even number of floats past ws
   const float inv_t = 1.0f / sqrtf((float)C);
   int rc;
   // 1. qp[v][j] = w_qkvs[j] . q[v]
   if ((rc = launch_rowdot(w_qkvs, H * C, C, q, nv, C, 0, H * C, nullptr, nullptr, 0, sv + L.qp, (long)H * C, 1.f,
-                          st, sv + L.r, (long)H * nv * C)))
+                          st, (float*)r, 2L * H * nv * C)))
     return rc;
   // 2. r[h][v][k] = sum_d w_qkvs[h*C+d][k] qp[v][h*C+d] / sqrt(C)  (r cleared by step 1's launch)
-  if ((rc = launch_coldot(w_qkvs, H, C, C, sv + L.qp, nv, (long)H * C, sv + L.r, inv_t, st))) return rc;
+  if ((rc = launch_coldot(w_qkvs, H, C, C, sv + L.qp, nv, (long)H * C, r, inv_t, st))) return rc;
   // 3. chunk partials over the token map
   dim3 g3(nchunk, B);
   float* sc_out = saved ? sv + L.sc : nullptr;
   if (H == 1)
-    hipLaunchKernelGGL((attn_partial_kernel<2>), g3, dim3(256), 0, st, sv + L.r, f, hw, nv, part_g, part_ml, sc_out,
+    hipLaunchKernelGGL((attn_partial_kernel<2>), g3, dim3(256), 0, st, (const double*)r, f, hw, nv, part_g, part_ml, sc_out,
                        p_attn, seed);
   else if (H == 2)
-    hipLaunchKernelGGL((attn_partial_kernel<4>), g3, dim3(256), 0, st, sv + L.r, f, hw, nv, part_g, part_ml, sc_out,
+    hipLaunchKernelGGL((attn_partial_kernel<4>), g3, dim3(256), 0, st, (const double*)r, f, hw, nv, part_g, part_ml, sc_out,
                        p_attn, seed);
   else
-    hipLaunchKernelGGL((attn_partial_kernel<8>), g3, dim3(256), 0, st, sv + L.r, f, hw, nv, part_g, part_ml, sc_out,
+    hipLaunchKernelGGL((attn_partial_kernel<8>), g3, dim3(256), 0, st, (const double*)r, f, hw, nv, part_g, part_ml, sc_out,
                        p_attn, seed);
   CWT_LAUNCH_CHECK();
   // 4. combine -> g[h][v][C]
