@@ -453,6 +453,25 @@ int cwt_debug_adapt_form(int form, int* out6) {
   return 0;
 }
 
+int cwt_debug_cp4d_plan(int dir, int B, int hA, int wA, int hB, int wB, int cin, int cout, int variant, int cu, int occ,
+                        int* out16) {
+  CWT_CHECK(out16 && dir >= 0 && dir <= 2 && B >= 1 && hA >= 1 && wA >= 1 && hB >= 1 && wB >= 1, "bad arguments");
+  const auto plan = dir == 0 ? cp4d_plan_fwd : dir == 1 ? cp4d_plan_dgrad : cp4d_plan_wgrad;
+  const Cp4dPlan p = plan(B, hA, wA, hB, wB, cin, cout, variant, cp4d_env(), cu, occ);
+  const int v[16] = {p.rc, p.form, p.cin, p.cout, p.mode, p.pf, p.gx,    p.gy,
+                     p.gz, p.wc,   p.nsa, p.ntiles, p.order, p.dbg, p.G, p.n};
+  std::copy(v, v + 16, out16);
+  return p.rc ? fail(p.rc, p.msg) : 0;
+}
+
+int cwt_debug_cp4d_form(int form, char* buf, int64_t cap) {
+  const Cp4dFormInfo f = cp4d_form_info(form);
+  if (!f.name) return fail(CWT_EARG, "no such consensus-layer form (cp4d_plan.h)");
+  return copy_text(std::string(f.name) + "\t" + f.kernel + "\t" + f.targs, buf, cap);
+}
+
+int cwt_debug_cp4d_wgrad_part_floats(void) { return cp4d_wgrad_part_floats(); }
+
 int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,
                        const float* res, int res_ld, int relu, float* y, int y_ld, int y_off, int bm, int bn,
@@ -509,6 +528,14 @@ int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, in
   if (!ctx || !x || !Wa || !ba || !Wb || !bb || !y) return fail(CWT_EARG, "null argument");
   if (B < 1 || hA < 1 || wA < 1 || hB < 1 || wB < 1) return fail(CWT_EARG, "bad shape");
   return launch_cp4d_layer_variant(x, B, hA, wA, hB, wB, cin, cout, Wa, ba, Wb, bb, y, variant, (hipStream_t)stream);
+}
+
+// the layer's input gradient dx [B][NA][NB][gout] (+)= from g [B][NA][NB][gin] (launch_cp4d_dgrad); variant as above
+int cwt_debug_cp4d_dgrad(cwt_ctx* ctx, const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout,
+                         const float* Wa, const float* Wb, float* dx, int accum, int variant, void* stream) {
+  if (!ctx || !g || !Wa || !Wb || !dx) return fail(CWT_EARG, "null argument");
+  if (B < 1 || hA < 1 || wA < 1 || hB < 1 || wB < 1) return fail(CWT_EARG, "bad shape");
+  return launch_cp4d_dgrad(g, B, hA, wA, hB, wB, gin, gout, Wa, Wb, dx, accum, (hipStream_t)stream, variant);
 }
 
 int cwt_debug_occupy(cwt_ctx* ctx, int nwg, int us, void* stream) {

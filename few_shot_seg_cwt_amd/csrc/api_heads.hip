@@ -279,7 +279,7 @@ int cwt_match_corr_backward(cwt_ctx* ctx, const float* corr, int B, int L, int h
     }
     np += 2 * (n + ch[l + 1]);
   }
-  const size_t part_floats = (size_t)cp4d_wgrad_part_floats(10, 10);
+  const size_t part_floats = (size_t)cp4d_wgrad_part_floats();
   float *g2d, *dy, *gA, *gm, *dx0, *part;
   int rc;
   if ((rc = ws(ctx, "mb.g2d", (size_t)E, &g2d)) || (rc = ws(ctx, "mb.dy", (size_t)E, &dy)) ||

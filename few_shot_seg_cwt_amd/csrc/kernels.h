@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "adapt_plan.h"
+#include "cp4d_plan.h"
 #include "common.h"
 
 namespace cwt {
@@ -236,7 +237,7 @@ int launch_ppm_field(const float* Q, int N, int h, int w, const int* bins, float
 // its adjoint: dQ [cells][9 * 512] from dF [N][h][w][512] (dR: R's shape, scratch)
 int launch_ppm_field_bwd(const float* dF, int N, int h, int w, const int* bins, float* dR, float* dQ, hipStream_t st);
 
-// ---- MatchNet / MMN backward (match_bwd.hip; launch_cp4d_dgrad in match.hip) ----
+// ---- MatchNet / MMN backward (match_bwd.hip) ----
 struct MmBwdWs {  // MutualMatching backward scratch, per (b, c): rows NA, columns NB, row blocks of 16
   float* rowmax;
   int* rowarg;
@@ -250,13 +251,6 @@ struct MmBwdWs {  // MutualMatching backward scratch, per (b, c): rows NA, colum
 int launch_mutual_matching_bwd(const float* x, const float* dy, int B, int NA, int NB, int C, float* dx,
                                const MmBwdWs& ws, hipStream_t st);
 int launch_relu_mask(const float* g, const float* out, long n, float* gm, hipStream_t st);
-int cp4d_wgrad_part_floats(int cin, int cout);
-int launch_cp4d_wgrad_mfma(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
-                           int G, float* part, hipStream_t st);
-int launch_cp4d_wgrad(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
-                      float* part, size_t part_floats, float* dWa, float* dWb, float* db1, float* db2, hipStream_t st);
-int launch_cp4d_dgrad(const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout, const float* Wa,
-                      const float* Wb, float* dx, int accum, hipStream_t st);
 int launch_match_softmax_bwd(const float* P, int ldp, const float* dA, int rows, int NB, float temp, int accum,
                              float* g, hipStream_t st);
 int launch_token_norm(const float* x, long T, int C, float eps, float* xn, float* nrm, hipStream_t st);
@@ -378,6 +372,17 @@ int launch_corr(const float* q, const float* k, int B, int Pq, int Pk, int C, fl
                 hipStream_t st);
 int launch_gemm_abt(const float* A, const float* Bm, int B, int M, int N, int K, float* Cm, hipStream_t st);
 
+// ---- cp4d.hip: the CenterPivotConv4d consensus layer, each launch as cp4d_plan.h plans it ----
+int launch_cp4d_layer(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout, const float* Wa,
+                      const float* ba, const float* Wb, const float* bb, float* y, hipStream_t st);
+int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
+                              const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
+                              hipStream_t st);
+int launch_cp4d_dgrad(const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout, const float* Wa,
+                      const float* Wb, float* dx, int accum, hipStream_t st, int variant = 0);
+int launch_cp4d_wgrad(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
+                      float* part, size_t part_floats, float* dWa, float* dWb, float* db1, float* db2, hipStream_t st);
+
 // ---- match.hip ----
 int launch_mutual_matching(const float* x, int B, int NA, int NB, int C, float* y, float* rowmax, float* colpart,
                            float* colmax, hipStream_t st);
@@ -385,11 +390,6 @@ int launch_mutual_matching_sum(const float* x, const float* x2, int B, int NA, i
                                float* colpart, float* colmax, hipStream_t st);
 int launch_mutual_matching_planar2(const float* x, int B, int NA, int NB, float* y, float* rowmax, float* colpart,
                                    float* colmax, hipStream_t st);
-int launch_cp4d_layer(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout, const float* Wa,
-                      const float* ba, const float* Wb, const float* bb, float* y, hipStream_t st);
-int launch_cp4d_layer_variant(const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
-                              const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
-                              hipStream_t st);
 int launch_to_channels_last(const float* x, int B, int C, long P, float* y, hipStream_t st);
 int launch_add_inplace(float* y, const float* x, long n, hipStream_t st);
 int launch_match_softmax(const float* corr, int B, int NA, int NB, float temp, int ldp, float* P, hipStream_t st);

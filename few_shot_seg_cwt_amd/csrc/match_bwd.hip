@@ -217,221 +217,6 @@ int launch_relu_mask(const float* g, const float* out, long n, float* gm, hipStr
   return 0;
 }
 
-// ---- CenterPivotConv4d weight / bias gradients (conv4d.py:40-62) ----
-// dWa[o][c][tap] = sum over (a, b) of gm[a][b][o] x[a + tap - 1][b][c] (zero padding), dWb the
-// same over the b plane, db[o] = sum gm[a][b][o] (conv1's and conv2's biases both).  Workgroups
-// stride over 2x8 (a) by 2x8 (b) tiles, stage the tile's cross-shaped input and its gradient in
-// LDS, and keep their partial sums in registers: thread = one (side, tap, o) entry with CIN
-// accumulators, 256 / (18 COUT) thread groups over the tile's 256 pairs.  Partials per
-// workgroup [G][18 COUT CIN + COUT], summed in workgroup order by cp4d_wgrad_reduce_kernel.
-constexpr int WG_TAH = 2, WG_TAW = 8, WG_TBH = 2, WG_TBW = 8;
-constexpr int WG_NA = WG_TAH * WG_TAW, WG_NB = WG_TBH * WG_TBW;
-constexpr int WG_HA = (WG_TAH + 2) * (WG_TAW + 2), WG_HB = (WG_TBH + 2) * (WG_TBW + 2);
-
-template <int CIN, int COUT>
-__global__ __launch_bounds__(256) void cp4d_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gm,
-                                                         int B, int hA, int wA, int hB, int wB,
-                                                         float* __restrict__ part) {
-  constexpr int NE = 18 * COUT;
-  constexpr int NG = 256 / NE;
-  static_assert(NG >= 1, "COUT <= 14");
-  __shared__ float xa[WG_HA][WG_NB][CIN];
-  __shared__ float xb[WG_NA][WG_HB][CIN];
-  __shared__ float gl[WG_NA * WG_NB][COUT];
-  __shared__ float red[NG * NE][CIN + 1];
-  const int NA = hA * wA, NB = hB * wB;
-  const int t = threadIdx.x;
-  const int e = t % NE, grp = t / NE;
-  const bool active = grp < NG;
-  const int side = e / (9 * COUT), tap = (e / COUT) % 9, o = e % COUT;
-  const int ky = tap / 3, kx = tap - 3 * (tap / 3);
-  float acc[CIN];
-#pragma unroll
-  for (int c = 0; c < CIN; ++c) acc[c] = 0.f;
-  float bacc = 0.f;
-  const int ntaw = (wA + WG_TAW - 1) / WG_TAW, ntah = (hA + WG_TAH - 1) / WG_TAH;
-  const int ntbw = (wB + WG_TBW - 1) / WG_TBW, ntbh = (hB + WG_TBH - 1) / WG_TBH;
-  const long ntb = (long)ntbh * ntbw, nta = (long)ntah * ntaw, ntiles = (long)B * nta * ntb;
-  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const long tb = tile % ntb, rest = tile / ntb;
-    const long ta = rest % nta, bz = rest / nta;
-    const int ha0 = (int)(ta / ntaw) * WG_TAH, wa0 = (int)(ta % ntaw) * WG_TAW;
-    const int hb0 = (int)(tb / ntbw) * WG_TBH, wb0 = (int)(tb % ntbw) * WG_TBW;
-    const float* xz = x + bz * NA * NB * CIN;
-    const float* gz = gm + bz * NA * NB * COUT;
-    __syncthreads();  // the previous tile's LDS reads are done
-    for (int i = t; i < WG_HA * WG_NB * CIN; i += 256) {  // a halo box at the tile's b positions
-      const int c = i % CIN, p = i / CIN;
-      const int bi = p % WG_NB, ai = p / WG_NB;
-      const int ha = ha0 - 1 + ai / (WG_TAW + 2), wa = wa0 - 1 + ai % (WG_TAW + 2);
-      const int hb = hb0 + bi / WG_TBW, wb = wb0 + bi % WG_TBW;
-      const bool in = (unsigned)ha < (unsigned)hA && (unsigned)wa < (unsigned)wA && hb < hB && wb < wB;
-      (&xa[0][0][0])[i] = in ? xz[((long)(ha * wA + wa) * NB + hb * wB + wb) * CIN + c] : 0.f;
-    }
-    for (int i = t; i < WG_NA * WG_HB * CIN; i += 256) {  // b halo box at the tile's a positions
-      const int c = i % CIN, p = i / CIN;
-      const int bi = p % WG_HB, ai = p / WG_HB;
-      const int ha = ha0 + ai / WG_TAW, wa = wa0 + ai % WG_TAW;
-      const int hb = hb0 - 1 + bi / (WG_TBW + 2), wb = wb0 - 1 + bi % (WG_TBW + 2);
-      const bool in = ha < hA && wa < wA && (unsigned)hb < (unsigned)hB && (unsigned)wb < (unsigned)wB;
-      (&xb[0][0][0])[i] = in ? xz[((long)(ha * wA + wa) * NB + hb * wB + wb) * CIN + c] : 0.f;
-    }
-    for (int i = t; i < WG_NA * WG_NB * COUT; i += 256) {  // the output gradient at the tile's pairs
-      const int oo = i % COUT, p = i / COUT;
-      const int ai = p / WG_NB, bi = p % WG_NB;
-      const int ha = ha0 + ai / WG_TAW, wa = wa0 + ai % WG_TAW;
-      const int hb = hb0 + bi / WG_TBW, wb = wb0 + bi % WG_TBW;
-      const bool in = ha < hA && wa < wA && hb < hB && wb < wB;
-      (&gl[0][0])[i] = in ? gz[((long)(ha * wA + wa) * NB + hb * wB + wb) * COUT + oo] : 0.f;
-    }
-    __syncthreads();
-    if (active) {
-      for (int p = grp; p < WG_NA * WG_NB; p += NG) {
-        const int ai = p / WG_NB, bi = p - ai * WG_NB;
-        const float gv = gl[p][o];
-        const float* xv = side == 0
-                              ? xa[(ai / WG_TAW + ky) * (WG_TAW + 2) + ai % WG_TAW + kx][bi]
-                              : xb[ai][(bi / WG_TBW + ky) * (WG_TBW + 2) + bi % WG_TBW + kx];
-#pragma unroll
-        for (int c = 0; c < CIN; ++c) acc[c] = fmaf(gv, xv[c], acc[c]);
-        bacc += gv;
-      }
-    }
-  }
-  __syncthreads();
-  if (active) {
-#pragma unroll
-    for (int c = 0; c < CIN; ++c) red[t][c] = acc[c];
-    red[t][CIN] = bacc;
-  }
-  __syncthreads();
-  if (t < NE) {
-    float s[CIN + 1];
-#pragma unroll
-    for (int c = 0; c <= CIN; ++c) s[c] = red[t][c];
-    for (int g = 1; g < NG; ++g)
-#pragma unroll
-      for (int c = 0; c <= CIN; ++c) s[c] += red[g * NE + t][c];
-    float* pw = part + (long)blockIdx.x * (NE * CIN + COUT);
-#pragma unroll
-    for (int c = 0; c < CIN; ++c) pw[t * CIN + c] = s[c];
-    if (t < COUT) pw[NE * CIN + t] = s[CIN];  // side 0, tap 0, o = t
-  }
-}
-
-// sum the partials in workgroup order; dWa / dWb [COUT][CIN][9] accumulate, and db1 / db2 [COUT]
-// unless bias == 0 (cp4d_bias_grad_f64 sums those)
-__global__ void cp4d_wgrad_reduce_kernel(const float* __restrict__ part, int G, int CIN, int COUT, float* dWa,
-                                         float* dWb, float* db1, float* db2, int bias) {
-  const int NE = 18 * COUT, n = NE * CIN + COUT;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n || (!bias && idx >= NE * CIN)) return;
-  float s = 0.f;
-  for (int g = 0; g < G; ++g) s += part[(long)g * n + idx];
-  if (idx < NE * CIN) {
-    const int e = idx / CIN, c = idx - e * CIN;
-    const int side = e / (9 * COUT), tap = (e / COUT) % 9, o = e % COUT;
-    float* W = side ? dWb : dWa;
-    W[(o * CIN + c) * 9 + tap] += s;
-  } else {
-    const int o = idx - NE * CIN;
-    db1[o] += s;
-    db2[o] += s;
-  }
-}
-
-// The bias gradients db1 = db2 += sum over every (a, b) pair of gm[p][o]: a sum of up to B (hA wA)
-// (hB wB) terms whose ReLU-masked values cancel heavily (the last consensus layer's single bias is
-// a few 1e-3 of sum |gm|), so it is accumulated in double, in a fixed order: chunks of
-// CB64_ROWS rows per workgroup (a thread's rows strided by 256, then a fixed LDS tree), then the
-// chunks in order.  Deterministic and accurate to the fp32 rounding of the result.
-constexpr int CB64_ROWS = 16384, CB64_MAXC = 16;
-__global__ __launch_bounds__(256) void colsum_f64_part_kernel(const float* __restrict__ X, long R, int Cc,
-                                                              double* __restrict__ part) {
-  __shared__ double red[256][CB64_MAXC + 1];
-  const int t = threadIdx.x;
-  const long r0 = (long)blockIdx.x * CB64_ROWS;
-  const long r1 = min(R, r0 + CB64_ROWS);
-  double acc[CB64_MAXC];
-#pragma unroll
-  for (int o = 0; o < CB64_MAXC; ++o) acc[o] = 0.0;
-  for (long r = r0 + t; r < r1; r += 256)
-#pragma unroll
-    for (int o = 0; o < CB64_MAXC; ++o)
-      if (o < Cc) acc[o] += (double)X[r * Cc + o];
-#pragma unroll
-  for (int o = 0; o < CB64_MAXC; ++o) red[t][o] = acc[o];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (t < w)
-      for (int o = 0; o < Cc; ++o) red[t][o] += red[t + w][o];
-    __syncthreads();
-  }
-  if (t < Cc) part[(long)blockIdx.x * Cc + t] = red[0][t];
-}
-
-__global__ void colsum_f64_final_kernel(const double* __restrict__ part, int nch, int Cc, float* db1, float* db2) {
-  const int o = threadIdx.x;
-  if (o >= Cc) return;
-  double s = 0.0;
-  for (int c = 0; c < nch; ++c) s += part[(long)c * Cc + o];
-  db1[o] = (float)((double)db1[o] + s);
-  if (db2) db2[o] = (float)((double)db2[o] + s);
-}
-
-// workgroups of the weight-gradient pass: 512 for the 10 -> 10 layer (two per CU by LDS), 2048 for
-// the thinner layers (less LDS each; measured 0.52 against 1.26 ms for 2 -> 10 at 60^2); 256 per
-// channel chunk for the chunked L -> 10 form (cp4d_nc_wgrad_kernel: its partials are 180 L + 10 floats)
-static bool wgrad_chunked(int cin, int cout) { return cout == 10 && cin != 1 && cin != 2 && cin != 10; }
-static int wgrad_grid(int cin, int cout) { return wgrad_chunked(cin, cout) ? 256 : cin * cout >= 100 ? 512 : 2048; }
-int cp4d_wgrad_part_floats(int cin, int cout) {
-  (void)cin;
-  (void)cout;
-  // the largest of the layers, the chunked form at CWT_MATCH_MAX_L included
-  return std::max(std::max(512 * (18 * 10 * 10 + 10), 2048 * (18 * 10 * 2 + 10)), 256 * (18 * 10 * CWT_MATCH_MAX_L + 10));
-}
-
-int launch_cp4d_wgrad(const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin, int cout,
-                      float* part, size_t part_floats, float* dWa, float* dWb, float* db1, float* db2,
-                      hipStream_t st) {
-  // the chunked form walks the matrix-core kernels' 4 x 4 by 4 x 4 tiles: its grid is sized by their count
-  const long ntiles = wgrad_chunked(cin, cout)
-                          ? (long)B * cdiv(hA, 4) * cdiv(wA, 4) * cdiv(hB, 4) * cdiv(wB, 4)
-                          : (long)B * cdiv(hA, WG_TAH) * cdiv(wA, WG_TAW) * cdiv(hB, WG_TBH) * cdiv(wB, WG_TBW);
-  const int G = (int)std::min<long>(wgrad_grid(cin, cout), ntiles);
-  const int n = 18 * cout * cin + cout;
-  if ((size_t)G * n > part_floats) return fail(CWT_ESTATE, "cp4d wgrad: partial workspace too small");
-  static const bool scalar = getenv("CWT_WGRAD_SCALAR") && getenv("CWT_WGRAD_SCALAR")[0] == '1';  // A/B only
-  if (!scalar) {
-    int rc = launch_cp4d_wgrad_mfma(x, gm, B, hA, wA, hB, wB, cin, cout, G, part, st);
-    if (rc) return rc;
-  } else {
-#define CWT_WG(CI, CO)                                                                                        \
-  if (cin == CI && cout == CO) {                                                                              \
-    hipLaunchKernelGGL((cp4d_wgrad_kernel<CI, CO>), dim3(G), dim3(256), 0, st, x, gm, B, hA, wA, hB, wB, part); \
-    CWT_LAUNCH_CHECK();                                                                                       \
-  } else
-    CWT_WG(1, 10)
-    CWT_WG(2, 10)
-    CWT_WG(10, 10)
-    CWT_WG(10, 1)
-    return fail(CWT_EARG, "cp4d wgrad: channels (1|2 -> 10, 10 -> 10, 10 -> 1) only");
-#undef CWT_WG
-  }
-  hipLaunchKernelGGL(cp4d_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)part, G, cin, cout,
-                     dWa, dWb, db1, db2, 0);
-  CWT_LAUNCH_CHECK();
-  // the biases in double (the partials above are consumed: their workspace takes the chunks)
-  const long R = (long)B * hA * wA * hB * wB;
-  const int nch = (int)cdiv(R, (long)CB64_ROWS);
-  if (cout > CB64_MAXC || (size_t)nch * cout * 2 > part_floats) return fail(CWT_ESTATE, "cp4d bias sum: workspace");
-  hipLaunchKernelGGL(colsum_f64_part_kernel, dim3(nch), dim3(256), 0, st, gm, R, cout, (double*)part);
-  CWT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(colsum_f64_final_kernel, dim3(1), dim3(64), 0, st, (const double*)part, nch, cout, db1, db2);
-  CWT_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- softmax(temp * corr2d) readout backward (match.py:151-153) ----
 // g[a][n] (+)= temp * P[a][n] * (dA[a][n] - sum_m P[a][m] dA[a][m]); one workgroup per row
 __global__ __launch_bounds__(256) void match_softmax_bwd_kernel(const float* __restrict__ P, int ldp,

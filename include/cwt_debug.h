@@ -152,6 +152,29 @@ int cwt_debug_splitk_epilogue(cwt_ctx* ctx, const float* part, int nsplit, int M
 int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, int hB, int wB, int cin, int cout,
                          const float* Wa, const float* ba, const float* Wb, const float* bb, float* y, int variant,
                          void* stream);
+/* The layer's input gradient: dx [B][hA*wA][hB*wB][gout] = (accum ? dx : 0) + the transposed, flipped
+ * convolutions of g [B][hA*wA][hB*wB][gin] (gin the layer's output channels, gout its input channels;
+ * Wa / Wb [gin][gout][3][3] as the forward applied them; no bias, no ReLU).  variant as above:
+ * 0 the library's choice, 1 never the rolling window (the tile kernel cp4d_mfma_kernel<gin, 1> where
+ * gout = 10), 2 only it, 3 the channel-chunked kernel (cp4d_nc_dgrad_kernel; gin 10, gout 1..32). */
+int cwt_debug_cp4d_dgrad(cwt_ctx* ctx, const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout,
+                         const float* Wa, const float* Wb, float* dx, int accum, int variant, void* stream);
+
+/* The consensus layer's launch plan (csrc/cp4d_plan.h), on the host alone (no context, no device
+ * call; the CWT_CP4D_*, CWT_DGRAD_SCALAR and CWT_WGRAD_SCALAR knobs are read from the environment as
+ * every launch reads them).  dir 0 the forward, 1 the input gradient (cin = gin, cout = gout), 2 the
+ * weight gradient; variant as cwt_debug_cp4d_layer; cu, occ the device's CUs and the persistent
+ * kernel's workgroups per CU (the persistent forms' grid alone depends on them) -> out16 = rc, form
+ * (Cp4dForm), the kernel's template arguments cin, cout, mode, pf, the grid x, y, z in workgroups, wc,
+ * nsa (rolling window), ntiles, order, dbg (persistent forms), G, n (weight gradient: partials and
+ * floats per partial).  Returns rc: 0, or CWT_EARG with the launcher's message for a refused shape.
+ * cwt_debug_cp4d_form: form 0..11 -> buf = "name\tkernel\ttemplate arguments" (the plan fields the
+ * kernel is instantiated on, comma-separated, in order); CWT_EARG for any other form.
+ * cwt_debug_cp4d_wgrad_part_floats: the floats of the weight gradient's partial workspace. */
+int cwt_debug_cp4d_plan(int dir, int B, int hA, int wA, int hB, int wB, int cin, int cout, int variant, int cu,
+                        int occ, int* out16);
+int cwt_debug_cp4d_form(int form, char* buf, int64_t cap);
+int cwt_debug_cp4d_wgrad_part_floats(void);
 
 /* Timing-study hook of cwt_episode_tail: with CWT_TAIL_STAMPS=1 in the environment the tail runs a
  * separately compiled instantiation whose workgroups record s_memtime at each phase edge
