@@ -36,8 +36,10 @@ struct AdaptScalars {
   // deterministic): value = integer * fx_inv, integer = rint(partial * fx_scale), fx_scale = 2^k
   // with every sum below 2^58: |dW[1]_c| <= max|f| * sum_p |g_p| <= max|f| * sum_p w_{y_p} (the
   // loop's per-pixel CE gradients are w_y (p - onehot), unnormalised, and the bilinear adjoint
-  // keeps the L1 norm); the quantum 2^-k is ~2^-57 of that bound.  A non-finite f gives
-  // fx_scale 0 and fx_inv NaN: W becomes NaN, as the reference's would
+  // keeps the L1 norm); the quantum 2^-k is ~2^-57 of that bound.  A non-finite entry in f or in
+  // the initial W gives fx_scale 0, fx_inv NaN and lr_eff NaN: the first update makes every W NaN,
+  // as the reference's float sums would (a NaN gradient has no fixed-point image: its conversion to
+  // an integer is undefined and left finite garbage in W)
   double fx_scale, fx_inv;
 };
 
@@ -145,6 +147,12 @@ __global__ void adapt_setup_kernel(const unsigned long long* __restrict__ part, 
   red[0][t] = t < nblk ? part[2 * t] : 0ull;
   red[1][t] = t < nblk ? part[2 * t + 1] : 0ull;
   fred[t] = (fpart && t < nblk) ? fpart[(long)e * PREP_MAXBLK + t] : 0u;
+  if (fpart && w_in) {  // the episode's initial W [2][512]: a non-finite entry takes the exit of a non-finite f
+    const float* we = w_in + (long)e * w_stride;
+    unsigned wb = 0u;
+    for (int i = t; i < 1024; i += PREP_MAXBLK) wb = max(wb, __float_as_uint(fabsf(we[i])));
+    if (wb >= 0x7f800000u) fred[t] = wb;
+  }
   __syncthreads();
   for (int o = PREP_MAXBLK / 2; o > 0; o >>= 1) {  // integer sums / maxima: order-independent
     if (t < o) {
@@ -168,9 +176,10 @@ __global__ void adapt_setup_kernel(const unsigned long long* __restrict__ part, 
     // per-pixel gradients are unnormalised (the 1 / sum_p w_{y_p} rides in lr_eff), so
     // |dW[1]_c| <= max|f| * sumw
     const unsigned mb = fred[0];
-    if (mb >= 0x7f800000u) {  // NaN / Inf in f
+    if (mb >= 0x7f800000u) {  // NaN / Inf in f or in the initial W
       sc->fx_scale = 0.0;
       sc->fx_inv = __builtin_nan("");
+      sc->lr_eff = __builtin_nanf("");  // the step launches' update (they take no fx_inv)
     } else {
       const double bound = (double)__uint_as_float(mb) * (sumw > 1.0 ? sumw : 1.0);
       const int k = bound > 0.0 ? 57 - ilogb(bound) : 0;  // bound < 2^(ilogb + 1)

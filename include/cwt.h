@@ -177,6 +177,8 @@ size_t cwt_workspace_bytes(cwt_ctx* ctx);
  * W_inout: device fp32 [2,C] — W0 on entry, adapted weights on return.
  * Returns CWT_EARG on bad shapes. A mask without foreground yields an infinite class
  * weight exactly like the reference; the caller checks counts if it needs to raise.
+ * A non-finite entry in f_s or in W0 yields NaN in every entry of W from the first step on, as
+ * the reference's float sums do (iters = 0 returns W0 as it came).
  */
 int cwt_inner_adapt(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w,
                     int C, int S, float lr, int iters, float* W_inout, void* stream);
