@@ -55,6 +55,9 @@ SIGNATURES = {
                               _P]),
     "cwt_inner_adapt_tail": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P,
                                   _P, _P, _P, _P, _P]),
+    "cwt_inner_adapt_nway": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P]),
+    "cwt_relabel_support": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cwt_seg_metrics_nway": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cwt_seg_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "cwt_seg_metrics_pair": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cwt_seg_ce_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

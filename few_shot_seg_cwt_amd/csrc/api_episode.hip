@@ -84,6 +84,68 @@ int cwt_inner_adapt(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int 
   return cwt_inner_adapt_batch(ctx, f_s, s_label, 1, n, h, w, C, S, lr, iters, W_inout, stream);
 }
 
+int cwt_inner_adapt_nway(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w, int C, int S,
+                         int N, int fg_idx, float tp, float lr, int iters, float* W_inout, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(f_s && s_label && W_inout, "null buffer");
+  CWT_CHECK(C == 512, "C must be 512");
+  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+  CWT_CHECK(fg_idx >= -1 && fg_idx < N, "fg_idx must be -1 or in [0, N)");
+  CWT_CHECK(n >= 1 && h >= 2 && w >= 2 && iters >= 0, "bad sizes");
+  CWT_CHECK(S - 1 == 8 * (h - 1) && S - 1 == 8 * (w - 1), "need S-1 == 8*(h-1) == 8*(w-1)");
+  CWT_HIP(hipSetDevice(ctx->device));
+  size_t b_lbl, b_sc, b_acc, b_wb;
+  adapt_nway_ws_sizes(n, S, N, &b_lbl, &b_sc, &b_acc, &b_wb);
+  void *lbl, *sc, *acc, *wb;
+  int rc;
+  if ((rc = ensure_ws(ctx, "nway.lbl", b_lbl, &lbl)) || (rc = ensure_ws(ctx, "nway.sc", b_sc, &sc)) ||
+      (rc = ensure_ws(ctx, "nway.acc", b_acc, &acc)) || (rc = ensure_ws(ctx, "nway.wbuf", b_wb, &wb)))
+    return rc;
+  const AdaptNwayWs aws{(uint8_t*)lbl, sc, (unsigned long long*)acc, (float*)wb};
+  // per step 2 x (2*N*C*h*w*n) FLOPs; minimal bytes = f_s + labels once per step
+  Prof p(ctx, (hipStream_t)stream, "inner_adapt_nway x" + std::to_string(iters) + " N=" + std::to_string(N),
+         (double)iters * 2.0 * (2.0 * N * C * h * w * n), (double)iters * ((double)n * h * w * C * 4 + (double)n * S * S), 1);
+  rc = launch_adapt_nway(f_s, s_label, n, h, w, S, N, fg_idx, tp, lr, iters, W_inout, aws,
+                         ctx->use_graph ? &ctx->adapt_nway_graphs : nullptr, (hipStream_t)stream);
+  p.end();
+  return rc;
+}
+
+int cwt_relabel_support(cwt_ctx* ctx, const float* logits, const int64_t* s_label, int B, int N, int h, int w, int S,
+                        int idx_cls, int64_t* out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits && s_label && out, "null buffer");
+  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+  CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
+  CWT_CHECK(B >= 1 && B <= 64 && h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) && S <= 32768,
+            "need 1 <= B <= 64 and h, w, S >= 2");
+  CWT_HIP(hipSetDevice(ctx->device));
+  Prof p(ctx, (hipStream_t)stream, "relabel_support N=" + std::to_string(N), 10.0 * B * N * S * S,
+         16.0 * B * S * S + 4.0 * B * N * h * w);
+  const int rc = launch_relabel_support(logits, s_label, B, N, h, w, S, idx_cls, out, (hipStream_t)stream);
+  p.end();
+  return rc;
+}
+
+int cwt_seg_metrics_nway(cwt_ctx* ctx, const float* logits, const int64_t* target, int B, int N, int h, int w, int S,
+                         int idx_cls, float* iut_out, double* ce_out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits && target && iut_out, "null buffer");
+  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+  CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
+  CWT_CHECK(B >= 1 && B <= 64 && h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) && S <= 32768,
+            "need 1 <= B <= 64 and h, w, S >= 2");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void* cnt;
+  int rc;
+  if ((rc = ensure_ws(ctx, "nway.metrics", nway_metrics_ws_bytes(B), &cnt))) return rc;
+  Prof p(ctx, (hipStream_t)stream, "seg_metrics_nway N=" + std::to_string(N), 30.0 * B * N * S * S,
+         8.0 * B * S * S + 4.0 * B * N * h * w);
+  rc = launch_seg_metrics_nway(logits, target, B, N, h, w, S, idx_cls, iut_out, ce_out, cnt, (hipStream_t)stream);
+  p.end();
+  return rc;
+}
+
 int cwt_normalize(cwt_ctx* ctx, const float* f, int B, int P_per_b, int C, float* out, const float* W0,
                   float* logits0, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");

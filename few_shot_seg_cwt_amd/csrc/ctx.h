@@ -49,6 +49,7 @@ struct cwt_ctx {
   size_t ev_used = 0;
   // inner loop: captured graphs of the step sequence (disable with CWT_ADAPT_GRAPH=0)
   cwt::AdaptGraphCache adapt_graphs;
+  cwt::AdaptGraphCache adapt_nway_graphs;  // the N-way loop's linear step graphs (adapt_nway.hip)
   bool use_graph = true;
   // conv arithmetic (CWT_CONV_ARITH_*): fp32 width on the bf16 matrix cores, operands split three
   // ways in registers (default, CWT_CONV=x6); bf16x3 over S-layout activations (CWT_CONV=x3s,

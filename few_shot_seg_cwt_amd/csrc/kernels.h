@@ -304,6 +304,36 @@ size_t adapt_ws_sizes(int E, int n, int h, int w, int S, size_t* fws, size_t* lb
 int launch_seg_ce(const float* logits, const int64_t* target, int B, int h, int w, int S, float* loss_out,
                   float* dlogits, uint8_t* lbl_ws, AdaptScalars* sc, double* loss_num, hipStream_t st);
 
+// ---- adapt_nway.hip ----
+// The N-way inner loop (2 <= N <= 64 classes; pspnet.py:207-221 with model_util.py:76-97): step
+// launches only, captured as one linear graph where `cache` is given.  A label outside [0, N) is
+// ignored like 255, whether or not it equals 255.  fg_idx = -1: every class weight is 1.
+struct AdaptNwayWs {
+  uint8_t* lbl;             // [n][S][S]
+  void* sc;                 // the scalars, the call's pointers and the prep kernel's partial counts
+  unsigned long long* acc;  // [3][R][N][512] fixed-point dW slots
+  float* wbuf;              // [2][N][512]
+};
+int adapt_nway_replicas(int N);
+void adapt_nway_ws_sizes(int n, int S, int N, size_t* lbl, size_t* sc, size_t* acc, size_t* wbuf);
+int launch_adapt_nway(const float* f, const int64_t* lbl64, int n, int h, int w, int S, int N, int fg_idx, float tp,
+                      float lr, int iters, float* W, const AdaptNwayWs& ws, AdaptGraphCache* cache, hipStream_t st);
+
+// ---- nway_pixel.hip ----
+// Per-pixel N-way label operations on low-resolution logits [B][N][h][w], upsampled to S x S
+// (bilinear, align_corners=True) in registers; any h, w, S >= 2.
+// reset_spt_label (model_util.py:119-127): out = s == 0 ? (am == 1 ? idx_cls : am) : (s == 1 ? idx_cls : s),
+// am the argmax over N with class idx_cls's logit at -1000 (first maximal index).  The am == 1
+// branch is the reference's own order of assignments: background is filled with the pseudo-label
+// first, and then EVERY 1 -- a pseudo-label of base class 1 included -- becomes idx_cls.
+int launch_relabel_support(const float* logits, const int64_t* s_label, int B, int N, int h, int w, int S,
+                           int idx_cls, int64_t* out, hipStream_t st);
+// pred2bmask + intersectionAndUnionGPU(., 2, 255) + the NLL of log(compress_pred(.)) (model_util.py:158-175;
+// train_cca.py:348-370).  ws: nway_metrics_ws_bytes(B) bytes
+size_t nway_metrics_ws_bytes(int B);
+int launch_seg_metrics_nway(const float* logits, const int64_t* target, int B, int N, int h, int w, int S,
+                            int idx_cls, float* iut, double* ce, void* ws, hipStream_t st);
+
 // ---- seg.hip ----
 int launch_normalize(const float* f, int B, int Pb, float* out, const float* W0, float* logits0, hipStream_t st);
 // W's batch stride wstride: 2 * 512 (a classifier per image), or 0 for one shared [2][512]

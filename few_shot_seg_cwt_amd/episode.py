@@ -57,6 +57,27 @@ def inner_adapt(f_s: torch.Tensor, s_label: torch.Tensor, W: torch.Tensor, lr: f
     return W
 
 
+def inner_adapt_nway(f_s: torch.Tensor, s_label: torch.Tensor, W: torch.Tensor, lr: float, iters: int, fg_idx: int,
+                     tp: float = 1.0) -> torch.Tensor:
+    """N-way support-set inner loop, in place on W [N,512], 2 <= N <= 64 (pspnet.py:207-221 with
+    model_util.py:76-97: class weight 1 but for float32(float32(bg / fg) ** tp) on fg_idx; fg_idx = -1:
+    plain CE).  f_s [n,512,h,w] channels_last; s_label [n,S,S] int64, labels outside [0, N) ignored."""
+    _lib.require(f_s, "f_s")
+    _lib.require(s_label, "s_label", torch.int64)
+    _lib.require(W, "W")
+    n, Cc, h, w = f_s.shape
+    if not f_s.is_contiguous(memory_format=torch.channels_last):
+        f_s = f_s.contiguous(memory_format=torch.channels_last)
+    S = s_label.shape[-1]
+    lbl = s_label.reshape(n, S, S).contiguous()
+    if W.dim() != 2 or W.shape[1] != Cc or not W.is_contiguous():
+        raise ValueError(f"W must be a contiguous [N,{Cc}] tensor")
+    _lib.check(_lib.lib().cwt_inner_adapt_nway(_lib.ctx(W.device.index), _lib.ptr(f_s), _lib.ptr(lbl), n, h, w, Cc, S,
+                                               int(W.shape[0]), int(fg_idx), float(tp), float(lr), int(iters),
+                                               _lib.ptr(W), _lib.stream_ptr(W.device)), "cwt_inner_adapt_nway")
+    return W
+
+
 def inner_adapt_batch(f_s: torch.Tensor, s_label: torch.Tensor, W: torch.Tensor, lr: float, iters: int) -> torch.Tensor:
     """E independent inner loops in the same launches (cwt_inner_adapt_batch), in place on
     W [E,2,512].  f_s [E*n,512,h,w] channels_last (episode-major), s_label [E,n,S,S] or

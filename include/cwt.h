@@ -337,6 +337,57 @@ int cwt_seg_metrics_pair(cwt_ctx* ctx, const float* logits, const float* logits0
                          void* stream);
 
 /*
+ * N-way support-set inner loop, 2 <= N <= CWT_ADAPT_MAX_WAY classes: `iters` SGD steps of a
+ * bias-free N-way 1x1 classifier on f_s, loss = weighted CrossEntropy(ignore 255, mean) of the
+ * bilinear(align_corners=True) upsampled logits vs s_label.
+ * Replaces: pspnet.py:207-221 PSPNet.increment_inner_loop with model_util.py:76-97 Adapt_SegLoss /
+ *           weighted_adpt_ce_loss (nn.Conv2d(512,N,1) + F.interpolate + nn.CrossEntropyLoss(weight,
+ *           ignore_index=255) + backward + optim.SGD(lr)).
+ * Class weights: 1 for every class but fg_idx, float32(float32(bg / fg) ** tp) for fg_idx, fg the
+ * pixels labelled fg_idx and bg every other non-ignored pixel, counted on the device.  fg_idx = -1:
+ * every weight is 1 (SegLoss('ce')).
+ * f_s: device fp32 NHWC [n,h,w,C], C = 512, S - 1 == 8 (h - 1) == 8 (w - 1);  s_label: device int64
+ * [n,S,S].  A label outside [0, N) is ignored like 255, WHETHER OR NOT it equals 255.
+ * W_inout: device fp32 [N,C] -- W0 on entry, the adapted weights on return.
+ * No pixel labelled fg_idx: the infinite weight is used by no pixel and the result is the finite
+ * one of the reference's autograd.  Every pixel ignored: W comes back as it went in.  iters = 0
+ * returns W0.  A non-finite entry in f_s or W0 makes every entry of W NaN from the first step.
+ * Two calls on the same inputs give the same bits (integer sums between the steps).
+ * Returns CWT_EARG before any device call on bad shapes, N outside [2, 64], fg_idx outside [-1, N).
+ */
+#define CWT_ADAPT_MAX_WAY 64
+int cwt_inner_adapt_nway(cwt_ctx* ctx, const float* f_s, const int64_t* s_label, int n, int h, int w, int C, int S,
+                         int N, int fg_idx, float tp, float lr, int iters, float* W_inout, void* stream);
+
+/*
+ * The support labels of a class-incremental episode (model_util.py:119-127 reset_spt_label): the
+ * logits [B,N,h,w] are upsampled to S x S (bilinear, align_corners=True; any h, w, S >= 2), class
+ * idx_cls's logit is set to -1000, am = argmax over N (first maximal index, as torch.argmax), and
+ *   out = s == 0 ? (am == 1 ? idx_cls : am) : (s == 1 ? idx_cls : s).
+ * The am == 1 branch is the reference's own order of assignments: background is filled with the
+ * pseudo-label first, and then every 1 -- a background pixel predicted as base class 1 included --
+ * becomes idx_cls.  s_label, out: device int64 [B,S,S]; s_label is left untouched.
+ * Limits: 1 <= B <= 64, h, w, S >= 2, h*w <= 2^24, S <= 32768.
+ * CWT_EARG on bad shapes, N outside [2, 64], idx_cls outside [0, N).
+ */
+int cwt_relabel_support(cwt_ctx* ctx, const float* logits, const int64_t* s_label, int B, int N, int h, int w, int S,
+                        int idx_cls, int64_t* out, void* stream);
+
+/*
+ * Binary metrics of N-way logits [B,N,h,w] against a 0 / 1 / 255 target (model_util.py:158-175
+ * pred2bmask + compress_pred; train_cca.py:348-370 intersectionAndUnionGPU(., 2, 255) and the NLL
+ * of log(compress_pred(.))): the mask is argmax == idx_cls, p_fg = softmax_N(z_hi)[idx_cls].
+ * iut_out: device fp32 [B,3,2] (intersection, union, target per class);
+ * ce_out:  device fp64 [B,2] (sum, count) of -log p_fg where the target is 1 and -log(1 - p_fg)
+ *          where it is 0, or NULL; log(1 - p_fg) comes from the log-sum-exp of the other classes
+ *          and stays finite where p_fg rounds to 1.  Integer counts and fixed-order sums: bitwise
+ *          reproducible.  Limits: 1 <= B <= 64, h, w, S >= 2, h*w <= 2^24, S <= 32768.
+ *          CWT_EARG on bad shapes, N outside [2, 64], idx_cls outside [0, N).
+ */
+int cwt_seg_metrics_nway(cwt_ctx* ctx, const float* logits, const int64_t* target, int B, int N, int h, int w, int S,
+                         int idx_cls, float* iut_out, double* ce_out, void* stream);
+
+/*
  * Weighted CE of upsampled logits and its gradient w.r.t. the low-res logits, for the
  * outer loop (train.py:237-243,261-265): class weight [1, #bg/(#fg+1e-12)] from target,
  * loss = sum_p w_y * nll_p / sum_p w_y over non-ignored p.
