@@ -128,6 +128,7 @@ SIGNATURES = {
     "cwt_debug_cp4d_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_cp4d_form": (_I, [_I, C.c_char_p, _I64]),
     "cwt_debug_cp4d_wgrad_part_floats": (_I, []),
+    "cwt_debug_match_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I64]),
     "cwt_debug_conv_f32d": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I,
                                  _I, _I, _P]),
     "cwt_debug_conv_x6": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I,

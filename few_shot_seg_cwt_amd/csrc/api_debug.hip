@@ -6,6 +6,7 @@
 #include "../../include/cwt_debug.h"
 #include "conv_forms.h"
 #include "ctx.h"
+#include "match_plan.h"
 
 using namespace cwt;
 
@@ -471,6 +472,65 @@ int cwt_debug_cp4d_form(int form, char* buf, int64_t cap) {
 }
 
 int cwt_debug_cp4d_wgrad_part_floats(void) { return cp4d_wgrad_part_floats(); }
+
+int cwt_debug_match_plan(int dir, int B, int L, int h, int w, int symmetric, int cv4, int train, int readout,
+                         int want_d_corr, int want_d_v, char* buf, int64_t cap) {
+  CWT_CHECK(dir == 0 || dir == 1, "dir must be 0 (forward) or 1 (backward)");
+  const auto S = [](long v) { return std::to_string(v); };
+  std::string out;
+  const auto params = [&](const MatchParams& T, bool cv, int branches) {
+    static const char* const names[2][4] = {{"conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias"},
+                                            {"weight", "bias", "", ""}};
+    for (int l = 0; l < 3; ++l)
+      for (int s = 0; s < (cv ? 1 : 2); ++s) {
+        out += "param\t" + S(l) + "\t" + names[cv][2 * s] + "\t" + S(T.W[l][s]) + "\t" + S(T.nW[l]) + "\n";
+        out += "param\t" + S(l) + "\t" + names[cv][2 * s + 1] + "\t" + S(T.b[l][s]) + "\t" + S(T.nb[l]) + "\n";
+      }
+    out += "param\ttotal\t" + S(T.total) + "\n";
+    for (int br = 0; br < (cv ? 0 : branches); ++br)
+      for (int l = 0; l < 3; ++l)
+        out += "role\t" + S(br) + "\t" + S(l) + "\t" + S(T.Wa(l, br)) + "\t" + S(T.ba(l, br)) + "\t" + S(T.Wb(l, br)) +
+               "\t" + S(T.bb(l, br)) + "\n";
+  };
+  const auto one = [&](const std::string& name, const MatchBuf& b) {
+    if (b.floats)
+      out += "buf\t" + name + "\t" + (b.ws ? b.ws : "saved") + "\t" + S(b.off) + "\t" + S(b.floats) + "\t" +
+             (b.per_cv ? "Cv" : "1") + "\n";
+  };
+  if (dir == 0) {
+    const MatchPlan p = match_plan(B, L, h, w, symmetric != 0, cv4 != 0, train != 0, readout != 0, match_env());
+    CWT_CHECK(!p.rc, p.msg);
+    static const char* const mm1[] = {"direct", "planar2", "clast"};
+    static const char* const mm2[] = {"plain", "add", "sum"};
+    out += std::string("plan\tfwd\tmm1=") + mm1[p.mm1] + "\tlayers=" + (p.cv4 ? "cv4d" : "cp4d") + "\tbranches=" +
+           S(p.branches) + "\tfork=" + S(p.fork) + "\tmm2=" + mm2[p.mm2] + "\treadout=" + S(p.readout) + "\ttrain=" +
+           S(p.train) + "\n";
+    params(p.params, p.cv4, p.branches);
+    one("x0", p.x0);
+    for (int br = 0; br < 2; ++br)
+      for (int l = 0; l < 3; ++l) one("o" + S(br) + S(l), p.o[br][l]);
+    one("y", p.y), one("attn", p.attn), one("vt", p.vt);
+    if (p.train)
+      out += "saved\ttotal\t" + S(match_saved_layout(B, L, (long)h * w, symmetric != 0, readout != 0).total) + "\n";
+  } else {
+    const MatchBwdPlan p = match_bwd_plan(B, L, h, w, symmetric != 0, want_d_corr != 0, want_d_v != 0, readout != 0);
+    CWT_CHECK(!p.rc, p.msg);
+    out += "plan\tbwd\tbranches=" + S(p.branches) + "\td_corr=" + S(p.d_corr) + "\td_v=" + S(p.d_v) + "\treadout=" +
+           S(p.readout) + "\tclast=" + S(p.clast) + "\n";
+    params(p.params, false, p.branches);
+    const long E = (long)B * h * w * h * w;
+    const MatchSavedLayout& s = p.saved;
+    one("x0", match_in_saved(s.x0, E * L));
+    for (int br = 0; br < p.branches; ++br)
+      for (int l = 0; l < 3; ++l) one("o" + S(br) + S(l), match_in_saved(s.o[br][l], E * match_ch(L, l + 1)));
+    one("y", match_in_saved(s.y, E));
+    if (s.attn >= 0) one("attn", match_in_saved(s.attn, s.total - s.attn));
+    one("g2d", p.g2d), one("dy", p.dy), one("gA", p.gA), one("gm", p.gm), one("dx0", p.dx0), one("part", p.part);
+    one("xcl", p.xcl), one("dxcl", p.dxcl);
+    out += "saved\ttotal\t" + S(s.total) + "\n";
+  }
+  return copy_text(out, buf, cap);
+}
 
 int cwt_debug_conv_x6w(cwt_ctx* ctx, const float* x, int N, int Hi, int Wi, int Ci, const float* w_packed,
                        const float* scale, const float* shift, int Co, int k, int stride, int pad, int dil,

@@ -1,529 +1,10 @@
-// MatchNet, WeightAverage and DeTr entry points of libcwt.so (include/cwt.h), forward and backward.
-#include <cstdlib>
-
+// WeightAverage, the MMN blend and DeTr entry points of libcwt.so (include/cwt.h), forward and
+// backward (MatchNet's own entry points: api_match.hip).
 #include "ctx.h"
 
 using namespace cwt;
 
 extern "C" {
-
-int cwt_corr(cwt_ctx* ctx, const float* q, const float* k, int B, int Pq, int Pk, int C, float* sim, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(q && k && sim && B >= 1 && Pq >= 1 && Pk >= 1 && C >= 4 && C % 4 == 0, "bad arguments (C % 4 == 0)");
-  CWT_HIP(hipSetDevice(ctx->device));
-  float *qn, *kn;
-  int rc;
-  if ((rc = ws(ctx, "corr.q", (size_t)B * Pq * C, &qn)) || (rc = ws(ctx, "corr.k", (size_t)B * Pk * C, &kn))) return rc;
-  return launch_corr(q, k, B, Pq, Pk, C, qn, kn, sim, (hipStream_t)stream);
-}
-
-// ---- MatchNet (match.py:21-163, conv4d.py:11-62) ----
-static int mm_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, float** rowmax, float** colpart, float** colmax) {
-  int rc;
-  const long nrb = cdiv(NA, 8);  // row blocks of launch_mutual_matching (8 rows: vector forms; 16: scalar)
-  if ((rc = ws(ctx, "match.rowmax", (size_t)B * C * NA, rowmax)) ||
-      (rc = ws(ctx, "match.colpart", (size_t)B * C * nrb * NB, colpart)) ||
-      (rc = ws(ctx, "match.colmax", (size_t)B * C * NB, colmax)))
-    return rc;
-  return 0;
-}
-
-int cwt_mutual_matching(cwt_ctx* ctx, const float* x, int B, int NA, int NB, int C, float* y, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(x && y && B >= 1 && NA >= 1 && NB >= 1 && C >= 1 && C <= 64, "bad arguments");
-  CWT_HIP(hipSetDevice(ctx->device));
-  float *rm, *cp, *cm;
-  int rc;
-  if ((rc = mm_ws(ctx, B, NA, NB, C, &rm, &cp, &cm))) return rc;
-  return launch_mutual_matching(x, B, NA, NB, C, y, rm, cp, cm, (hipStream_t)stream);
-}
-
-// the activations the corr_forward backward reads (cwt_match_corr_forward_train), carved from one
-// caller buffer: x0 = MutualMatching(corr) channels-last [E][L], o[branch][layer] the ReLU outputs
-// [E][10], [E][10], [E][1], y = o[0][2] + o[1][2] [E] (E = B NA NB), attn [B][NA][ld32(NB)]
-struct MatchSaved {
-  float* x0;
-  float* o[2][3];
-  float* y;
-  float* attn;
-};
-static size_t match_saved_layout(float* base, int B, int L, long NA, int symmetric, int readout, MatchSaved* s) {
-  const long E = (long)B * NA * NA, ldp = (NA + 31) & ~31L;
-  size_t off = 0;
-  auto take = [&](long n) {
-    float* p = base ? base + off : nullptr;
-    off += (size_t)n;
-    return p;
-  };
-  MatchSaved d;
-  d.x0 = take(E * L);
-  for (int br = 0; br < 2; ++br)
-    for (int l = 0; l < 3; ++l) d.o[br][l] = (br == 0 || symmetric) ? take(E * (l < 2 ? 10 : 1)) : nullptr;
-  d.y = take(E);
-  d.attn = readout ? take((long)B * NA * ldp) : nullptr;
-  if (s) *s = d;
-  return off;
-}
-
-// CWT_MM_FUSE=1: the 2-channel correlation's transposition folded into MutualMatching's passes
-// and the symmetric branches' sum into the second MutualMatching (fewer passes over the 4-D map)
-static bool mm_fuse() {
-  static const bool on = getenv("CWT_MM_FUSE") && getenv("CWT_MM_FUSE")[0] == '1';
-  return on;
-}
-
-static int match_corr_forward(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
-                              int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
-                              void* stream, bool cv4, float* saved = nullptr) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr && nc_params && corr2d && B >= 1 && 1 <= L && L <= CWT_MATCH_MAX_L && h >= 1 && w >= 1,
-            "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
-  CWT_CHECK(!cv4 || L <= 2, "Conv4d ('cv4') layers take in_channel 1 or 2 only (CenterPivotConv4d: up to 32)");
-  CWT_CHECK(!weighted_v || (v && Cv >= 1), "weighted_v needs v");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const long NA = (long)h * w, NB = NA, P = NA * NB;
-  float *x0, *x1, *x2, *y1, *y2;
-  int rc;
-  if ((rc = ws(ctx, "match.x0", (size_t)B * P * L, &x0)) || (rc = ws(ctx, "match.x1", (size_t)B * P * 10, &x1)) ||
-      (rc = ws(ctx, "match.x2", (size_t)B * P * 10, &x2)) || (rc = ws(ctx, "match.y1", (size_t)B * P, &y1)) ||
-      (rc = ws(ctx, "match.y2", (size_t)B * P, &y2)))
-    return rc;
-  MatchSaved S;
-  if (saved) {
-    CWT_CHECK(!cv4, "the training forward keeps CenterPivotConv4d ('red') activations only");
-    match_saved_layout(saved, B, L, NA, symmetric, weighted_v != nullptr, &S);
-    x0 = S.x0;
-  }
-  float *rm, *cp, *cm;
-  if ((rc = mm_ws(ctx, B, (int)NA, (int)NB, L, &rm, &cp, &cm))) return rc;
-  Prof p(ctx, st, "match_corr_forward", 2.0 * B * P * 2 * (18.0 * L * 10 + 18.0 * 100 + 18.0 * 10), 4.0 * B * P * (L + 1));
-  // run_match_model: MutualMatching -> NeighConsensus -> MutualMatching (match.py:159-163)
-  if (L == 1) {
-    if ((rc = launch_mutual_matching(corr, B, (int)NA, (int)NB, 1, x0, rm, cp, cm, st))) return rc;
-  } else {
-    if (mm_fuse() && L == 2) {
-      if ((rc = launch_mutual_matching_planar2(corr, B, (int)NA, (int)NB, x0, rm, cp, cm, st))) return rc;
-    } else {
-      if ((rc = launch_to_channels_last(corr, B, L, P, x0, st))) return rc;
-      if ((rc = launch_mutual_matching(x0, B, (int)NA, (int)NB, L, x0, rm, cp, cm, st))) return rc;
-    }
-  }
-  const int ch[4] = {L, 10, 10, 1};
-  if (cv4) {
-    // Conv4d layers (conv4d.py:64-138): per layer weight [3][co][ci][3][3][3] (the reference's
-    // pre-permuted filter), bias [co]; the symmetric branch is the same stack with each filter's
-    // position pairs exchanged (cv4d_layer_kernel swap)
-    const float* cw[3][2];
-    const float* q = nc_params;
-    for (int l = 0; l < 3; ++l) {
-      cw[l][0] = q;
-      q += 81 * ch[l] * ch[l + 1];
-      cw[l][1] = q;
-      q += ch[l + 1];
-    }
-    for (int br = 0; br < (symmetric ? 2 : 1); ++br) {
-      const float* in = x0;
-      float* outs[3] = {x1, x2, br ? y2 : y1};
-      for (int l = 0; l < 3; ++l) {
-        if ((rc = launch_cv4d_layer(in, B, h, w, h, w, ch[l], ch[l + 1], cw[l][0], cw[l][1], br, outs[l], st)))
-          return rc;
-        in = outs[l];
-      }
-    }
-  } else {
-  // parameters per layer: conv1.weight [co][ci][3][3], conv1.bias [co], conv2.weight, conv2.bias
-  const float* lw[3][4];
-  {
-    const float* q = nc_params;
-    for (int l = 0; l < 3; ++l) {
-      const int n = ch[l + 1] * ch[l] * 9;
-      lw[l][0] = q; q += n;
-      lw[l][1] = q; q += ch[l + 1];
-      lw[l][2] = q; q += n;
-      lw[l][3] = q; q += ch[l + 1];
-    }
-  }
-  // branch 0: conv(x) (conv1 over the query positions a, conv2 over the support positions b);
-  // branch 1 (symmetric mode): conv(x^T)^T = the same stack with the two roles swapped.  The two
-  // branches are independent until their sum: branch 1 runs on the context's second stream
-  // (its own intermediate buffers), so one branch's store-bound layers overlap the other's
-  // MFMA-bound ones (CWT_MATCH_BRANCH_STREAMS=0: one after the other on the caller's stream)
-  static const bool two_streams = !(getenv("CWT_MATCH_BRANCH_STREAMS") && getenv("CWT_MATCH_BRANCH_STREAMS")[0] == '0');
-  const bool fork = symmetric && two_streams;
-  float *x1b = x1, *x2b = x2;
-  if (fork) {
-    if (!saved && ((rc = ws(ctx, "match.x1b", (size_t)B * P * 10, &x1b)) ||
-                   (rc = ws(ctx, "match.x2b", (size_t)B * P * 10, &x2b))))
-      return rc;
-    if (!ctx->aux) CWT_HIP(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-    if (!ctx->ev_fork) CWT_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    if (!ctx->ev_join) CWT_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    CWT_HIP(hipEventRecord(ctx->ev_fork, st));
-    CWT_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-  }
-  for (int br = 0; br < (symmetric ? 2 : 1); ++br) {
-    const float* in = x0;
-    const hipStream_t bst = (fork && br == 1) ? ctx->aux : st;
-    float* outs[3] = {br && fork ? x1b : x1, br && fork ? x2b : x2,
-                      br ? y2 : y1};
-    if (saved)
-      for (int l = 0; l < 3; ++l) outs[l] = S.o[br][l];
-    for (int l = 0; l < 3; ++l) {
-      const float* Wa = br ? lw[l][2] : lw[l][0];
-      const float* ba = br ? lw[l][3] : lw[l][1];
-      const float* Wb = br ? lw[l][0] : lw[l][2];
-      const float* bb = br ? lw[l][1] : lw[l][3];
-      if ((rc = launch_cp4d_layer(in, B, h, w, h, w, ch[l], ch[l + 1], Wa, ba, Wb, bb, outs[l], bst))) return rc;
-      in = outs[l];
-    }
-  }
-  if (fork) {
-    CWT_HIP(hipEventRecord(ctx->ev_join, ctx->aux));
-    CWT_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-  }
-  }
-  if (saved) {  // y = o[0][2] (+ o[1][2]) into its own slot: the ReLU outputs stay for the backward
-    CWT_HIP(hipMemcpyAsync(S.y, S.o[0][2], (size_t)B * P * 4, hipMemcpyDeviceToDevice, st));
-    if (symmetric && (rc = launch_add_inplace(S.y, (const float*)S.o[1][2], B * P, st))) return rc;
-    y1 = S.y;
-  } else if (symmetric && !mm_fuse() && (rc = launch_add_inplace(y1, y2, B * P, st))) {
-    return rc;
-  }
-  if ((rc = mm_ws(ctx, B, (int)NA, (int)NB, 1, &rm, &cp, &cm))) return rc;
-  if (!saved && symmetric && mm_fuse()) {  // MutualMatching of y1 + y2 (the sum folded into its two passes)
-    if ((rc = launch_mutual_matching_sum(y1, y2, B, (int)NA, (int)NB, corr2d, rm, cp, cm, st))) return rc;
-  } else if ((rc = launch_mutual_matching(y1, B, (int)NA, (int)NB, 1, corr2d, rm, cp, cm, st))) {
-    return rc;
-  }
-  if (weighted_v) {
-    // attn = softmax(temp * corr2d, dim=-1); weighted_v = bmm(v, attn^T) (match.py:151-153),
-    // here as tokens [B][NA][Cv] = attn . v
-    const int ldp = (int)((NB + 31) & ~31L);  // zero-padded to whole 32-deep K tiles (gemm_f32d)
-    float *pw, *vt;
-    if ((rc = ws(ctx, "match.attn", (size_t)B * NA * ldp, &pw)) ||
-        (rc = ws(ctx, "match.vt", (size_t)B * Cv * ldp, &vt)))
-      return rc;
-    if (saved) pw = S.attn;
-    if ((rc = launch_match_softmax(corr2d, B, (int)NA, (int)NB, temp, ldp, pw, st))) return rc;
-    if ((rc = launch_match_vt(v, B, (int)NB, Cv, ldp, vt, st))) return rc;
-    if ((rc = readout_gemm(ctx, pw, vt, B, (int)NA, Cv, ldp, weighted_v, st))) return rc;
-  }
-  p.end();
-  return 0;
-}
-
-int cwt_match_corr_forward(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
-                           int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
-                           void* stream) {
-  return match_corr_forward(ctx, corr, B, L, h, w, nc_params, symmetric, temp, v, Cv, corr2d, weighted_v, stream, false);
-}
-
-int cwt_match_corr_forward_cv4(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
-                               int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
-                               void* stream) {
-  return match_corr_forward(ctx, corr, B, L, h, w, nc_params, symmetric, temp, v, Cv, corr2d, weighted_v, stream, true);
-}
-
-// ---- MatchNet / MMN backward (match_bwd.hip) ----
-static int mm_bwd_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, MmBwdWs* w) {
-  const long nrb = cdiv(NA, 16), bc = (long)B * C;
-  int rc;
-  if ((rc = ws(ctx, "mb.rowmax", bc * NA, &w->rowmax)) || (rc = ws(ctx, "mb.rowarg", bc * NA, &w->rowarg)) ||
-      (rc = ws(ctx, "mb.colpv", bc * nrb * NB, &w->colpv)) || (rc = ws(ctx, "mb.colpi", bc * nrb * NB, &w->colpi)) ||
-      (rc = ws(ctx, "mb.colmax", bc * NB, &w->colmax)) || (rc = ws(ctx, "mb.colarg", bc * NB, &w->colarg)) ||
-      (rc = ws(ctx, "mb.srow", bc * NA, &w->srow)) || (rc = ws(ctx, "mb.scol", bc * NB, &w->scol)))
-    return rc;
-  return 0;
-}
-
-int cwt_match_corr_saved_floats(int B, int L, int h, int w, int symmetric, int readout, int64_t* n) {
-  if (!n || B < 1 || L < 1 || L > CWT_MATCH_MAX_L || h < 1 || w < 1)
-    return fail(CWT_EARG, "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
-  *n = (int64_t)match_saved_layout(nullptr, B, L, (long)h * w, symmetric, readout, nullptr);
-  return 0;
-}
-
-int cwt_match_corr_forward_train(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
-                                 int symmetric, float temp, const float* v, int Cv, float* corr2d, float* weighted_v,
-                                 float* saved, void* stream) {
-  if (!saved) return fail(CWT_EARG, "saved is NULL");
-  return match_corr_forward(ctx, corr, B, L, h, w, nc_params, symmetric, temp, v, Cv, corr2d, weighted_v, stream, false,
-                            saved);
-}
-
-int cwt_match_corr_backward(cwt_ctx* ctx, const float* corr, int B, int L, int h, int w, const float* nc_params,
-                            int symmetric, float temp, const float* v, int Cv, const float* saved,
-                            const float* d_corr2d, const float* d_weighted_v, float* d_corr, float* d_params,
-                            float* d_v, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr && nc_params && saved && d_params && B >= 1 && 1 <= L && L <= CWT_MATCH_MAX_L && h >= 1 && w >= 1,
-            "bad arguments (in_channel 1 .. CWT_MATCH_MAX_L = 32)");
-  CWT_CHECK(!d_weighted_v || (v && Cv >= 4 && Cv % 4 == 0), "d_weighted_v needs v and Cv % 4 == 0");
-  CWT_CHECK(!d_v || d_weighted_v, "d_v needs d_weighted_v");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const long NA = (long)h * w, NB = NA, P = NA * NB, E = (long)B * P, ldp = ld32(NB);
-  MatchSaved S;
-  match_saved_layout((float*)saved, B, L, NA, symmetric, d_weighted_v != nullptr, &S);
-  const int ch[4] = {L, 10, 10, 1};
-  const float* lw[3][4];
-  float* dlw[3][4];
-  long np = 0;
-  for (int l = 0; l < 3; ++l) {
-    const long n = (long)ch[l + 1] * ch[l] * 9;
-    const long off[4] = {np, np + n, np + n + ch[l + 1], np + 2 * n + ch[l + 1]};
-    for (int q = 0; q < 4; ++q) {
-      lw[l][q] = nc_params + off[q];
-      dlw[l][q] = d_params + off[q];
-    }
-    np += 2 * (n + ch[l + 1]);
-  }
-  const size_t part_floats = (size_t)cp4d_wgrad_part_floats();
-  float *g2d, *dy, *gA, *gm, *dx0, *part;
-  int rc;
-  if ((rc = ws(ctx, "mb.g2d", (size_t)E, &g2d)) || (rc = ws(ctx, "mb.dy", (size_t)E, &dy)) ||
-      (rc = ws(ctx, "mb.gA", (size_t)E * 10, &gA)) || (rc = ws(ctx, "mb.gm", (size_t)E * 10, &gm)) ||
-      (rc = ws(ctx, "mb.dx0", (size_t)E * L, &dx0)) || (rc = ws(ctx, "mb.part", part_floats, &part)))
-    return rc;
-  MmBwdWs mw;
-  if ((rc = mm_bwd_ws(ctx, B, (int)NA, (int)NB, L, &mw))) return rc;
-  Prof p(ctx, st, "match_corr_backward", 2.0 * 2.0 * B * P * 2 * (18.0 * L * 10 + 18.0 * 100 + 18.0 * 10),
-         4.0 * B * P * (L + 44));
-  CWT_HIP(hipMemsetAsync(d_params, 0, (size_t)np * 4, st));
-  // the gradient at corr2d: the caller's, plus the softmax readout's (match.py:151-153)
-  if (d_corr2d)
-    CWT_HIP(hipMemcpyAsync(g2d, d_corr2d, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
-  else
-    CWT_HIP(hipMemsetAsync(g2d, 0, (size_t)E * 4, st));
-  if (d_weighted_v) {
-    float* dA;
-    if ((rc = ws(ctx, "mb.dA", (size_t)E, &dA))) return rc;
-    for (int b = 0; b < B; ++b)  // dA = d_wv . v^T
-      if ((rc = gemm_nt(ctx, d_weighted_v + (long)b * NA * Cv, v + (long)b * NB * Cv, (int)NA, (int)NB, Cv,
-                        dA + (long)b * NA * NB, st)))
-        return rc;
-    if ((rc = launch_match_softmax_bwd(S.attn, (int)ldp, dA, (int)(B * NA), (int)NB, temp, 1, g2d, st))) return rc;
-    if (d_v) {  // d_v[b] = attn[b]^T . d_wv[b]
-      const long lda = ld32(NA);
-      float *pt, *dwt;
-      if ((rc = ws(ctx, "mb.PT", (size_t)B * ldp * lda, &pt)) || (rc = ws(ctx, "mb.dwvT", (size_t)B * Cv * lda, &dwt)))
-        return rc;
-      if ((rc = launch_match_vt(S.attn, B, (int)NA, (int)ldp, (int)lda, pt, st)) ||
-          (rc = launch_match_vt(d_weighted_v, B, (int)NA, Cv, (int)lda, dwt, st)))
-        return rc;
-      for (int b = 0; b < B; ++b)
-        if ((rc = gemm_nt(ctx, pt + (long)b * ldp * lda, dwt + (long)b * Cv * lda, (int)NB, Cv, (int)lda,
-                          d_v + (long)b * NB * Cv, st)))
-          return rc;
-    }
-  }
-  // the second MutualMatching (match.py:162)
-  if ((rc = launch_mutual_matching_bwd(S.y, g2d, B, (int)NA, (int)NB, 1, dy, mw, st))) return rc;
-  // NeighConsensus: both branches see the same output gradient (y = branch 0 + branch 1); branch 1
-  // applied conv2's filter over the a plane and conv1's over the b plane (match.py:75-80)
-  for (int br = 0; br < (symmetric ? 2 : 1); ++br) {
-    const float* gcur = dy;
-    for (int l = 2; l >= 0; --l) {
-      const int cin = ch[l], cout = ch[l + 1];
-      const float* out = S.o[br][l];
-      const float* in = l ? S.o[br][l - 1] : S.x0;
-      if ((rc = launch_relu_mask(gcur, out, E * cout, gm, st))) return rc;
-      const float* Wa = br ? lw[l][2] : lw[l][0];
-      const float* Wb = br ? lw[l][0] : lw[l][2];
-      float* dWa = br ? dlw[l][2] : dlw[l][0];
-      float* dWb = br ? dlw[l][0] : dlw[l][2];
-      if ((rc = launch_cp4d_wgrad(in, gm, B, h, w, h, w, cin, cout, part, part_floats, dWa, dWb, dlw[l][1], dlw[l][3],
-                                  st)))
-        return rc;
-      if (l > 0) {
-        if ((rc = launch_cp4d_dgrad(gm, B, h, w, h, w, cout, cin, Wa, Wb, gA, 0, st))) return rc;
-        gcur = gA;
-      } else if (d_corr) {
-        if ((rc = launch_cp4d_dgrad(gm, B, h, w, h, w, cout, cin, Wa, Wb, dx0, br, st))) return rc;
-      }
-    }
-  }
-  // the first MutualMatching (match.py:160), back to the caller's channel-first layout
-  if (d_corr) {
-    if (L == 1) {
-      if ((rc = launch_mutual_matching_bwd(corr, dx0, B, (int)NA, (int)NB, 1, d_corr, mw, st))) return rc;
-    } else {
-      float *xcl, *dxcl;
-      if ((rc = ws(ctx, "mb.xcl", (size_t)E * L, &xcl)) || (rc = ws(ctx, "mb.dxcl", (size_t)E * L, &dxcl))) return rc;
-      if ((rc = launch_to_channels_last(corr, B, L, P, xcl, st)) ||
-          (rc = launch_mutual_matching_bwd(xcl, dx0, B, (int)NA, (int)NB, L, dxcl, mw, st)) ||
-          (rc = launch_to_channels_first(dxcl, B, L, P, d_corr, st)))
-        return rc;
-    }
-  }
-  p.end();
-  return 0;
-}
-
-int cwt_corr_backward(cwt_ctx* ctx, const float* q, const float* k, int B, int Pq, int Pk, int C, const float* d_sim,
-                      float* dq, float* dk, int accum_q, int accum_k, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(q && k && d_sim && B >= 1 && Pq >= 1 && Pk >= 1 && C >= 1, "bad arguments");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const float eps = 1e-12f;
-  float *qn, *qr, *kn, *kr;
-  int rc;
-  if ((rc = ws(ctx, "cb.qn", (size_t)B * Pq * C, &qn)) || (rc = ws(ctx, "cb.qr", (size_t)B * Pq, &qr)) ||
-      (rc = ws(ctx, "cb.kn", (size_t)B * Pk * C, &kn)) || (rc = ws(ctx, "cb.kr", (size_t)B * Pk, &kr)))
-    return rc;
-  Prof p(ctx, st, "corr_backward", 2.0 * 2.0 * B * (double)Pq * Pk * C, 4.0 * B * ((double)Pq * Pk + 2.0 * (Pq + Pk) * C));
-  if ((rc = launch_token_norm(q, (long)B * Pq, C, eps, qn, qr, st)) ||
-      (rc = launch_token_norm(k, (long)B * Pk, C, eps, kn, kr, st)))
-    return rc;
-  if (dq) {  // d qn = d_sim . kn
-    const long ldk = ld32(Pk);
-    float *dsp, *knt, *dqn;
-    if ((rc = ws(ctx, "cb.dsp", (size_t)B * Pq * ldk, &dsp)) || (rc = ws(ctx, "cb.knT", (size_t)B * C * ldk, &knt)) ||
-        (rc = ws(ctx, "cb.dqn", (size_t)B * Pq * C, &dqn)))
-      return rc;
-    if ((rc = launch_copy_pad(d_sim, (long)B * Pq, Pk, (int)ldk, dsp, st)) ||
-        (rc = launch_match_vt(kn, B, Pk, C, (int)ldk, knt, st)))
-      return rc;
-    for (int b = 0; b < B; ++b)
-      if ((rc = gemm_nt(ctx, dsp + (long)b * Pq * ldk, knt + (long)b * C * ldk, Pq, C, (int)ldk, dqn + (long)b * Pq * C,
-                        st)))
-        return rc;
-    if ((rc = launch_token_norm_bwd(qn, qr, dqn, (long)B * Pq, C, C, eps, accum_q, dq, st))) return rc;
-  }
-  if (dk) {  // d kn = d_sim^T . qn
-    const long ldq = ld32(Pq);
-    float *dst, *qnt, *dkn;
-    if ((rc = ws(ctx, "cb.dsT", (size_t)B * Pk * ldq, &dst)) || (rc = ws(ctx, "cb.qnT", (size_t)B * C * ldq, &qnt)) ||
-        (rc = ws(ctx, "cb.dkn", (size_t)B * Pk * C, &dkn)))
-      return rc;
-    if ((rc = launch_match_vt(d_sim, B, Pq, Pk, (int)ldq, dst, st)) ||
-        (rc = launch_match_vt(qn, B, Pq, C, (int)ldq, qnt, st)))
-      return rc;
-    for (int b = 0; b < B; ++b)
-      if ((rc = gemm_nt(ctx, dst + (long)b * Pk * ldq, qnt + (long)b * C * ldq, Pk, C, (int)ldq, dkn + (long)b * Pk * C,
-                        st)))
-        return rc;
-    if ((rc = launch_token_norm_bwd(kn, kr, dkn, (long)B * Pk, C, C, eps, accum_k, dk, st))) return rc;
-  }
-  p.end();
-  return 0;
-}
-
-int cwt_sce_descriptor(cwt_ctx* ctx, const float* x, int B, int h, int w, int C, int k, int ldg, float* g,
-                       void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(x && g && B >= 1 && h >= 1 && w >= 1 && C >= 1, "bad arguments");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  Prof p(ctx, st, "sce_descriptor", 2.0 * B * h * w * (double)k * k * C, 4.0 * B * h * w * ((double)C + ldg));
-  int rc;
-  if ((rc = launch_sce_descriptor(x, B, h, w, C, k, ldg, g, st))) return rc;
-  p.end();
-  return 0;
-}
-
-int cwt_channel_sum(cwt_ctx* ctx, const float* x, int B, int L, int64_t P, float* y, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(x && y && B >= 1 && L >= 1 && P >= 1, "bad arguments");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  Prof p(ctx, st, "channel_sum", (double)B * L * P, 4.0 * B * P * (L + 1));
-  int rc;
-  if ((rc = launch_channel_sum(x, B, L, (long)P, y, st))) return rc;
-  p.end();
-  return 0;
-}
-
-int cwt_match_masks(cwt_ctx* ctx, float* corr2d, int B, int NA, int NB, const uint8_t* ig_mask,
-                    const int64_t* s_mask, float* inconsistent, void* stream) {
-  return cwt_match_masks_train(ctx, corr2d, B, NA, NB, ig_mask, s_mask, inconsistent, 0.f, 0, stream);
-}
-
-int cwt_match_masks_train(cwt_ctx* ctx, float* corr2d, int B, int NA, int NB, const uint8_t* ig_mask,
-                          const int64_t* s_mask, float* inconsistent, float drop_p, uint64_t seed, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr2d && B >= 1 && NA >= 1 && NB >= 1 && drop_p >= 0.f && drop_p < 1.f, "bad arguments");
-  CWT_CHECK(!s_mask || inconsistent, "the cycle mask needs inconsistent");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  int *q2k = nullptr, *pi = nullptr;
-  float* pv = nullptr;
-  int rc;
-  if (s_mask && ((rc = ws(ctx, "match.q2k", (size_t)B * NA, &q2k)) || (rc = ws(ctx, "match.colv", (size_t)B * 16 * NB, &pv)) ||
-                 (rc = ws(ctx, "match.coli", (size_t)B * 16 * NB, &pi))))
-    return rc;
-  Prof p(ctx, st, "match_masks", 0.0, 4.0 * B * NA * NB * (s_mask ? 4 : 2));
-  if ((rc = launch_match_masks(corr2d, B, NA, NB, ig_mask, s_mask, inconsistent, q2k, pv, pi, st, drop_p,
-                               (unsigned long long)seed)))
-    return rc;
-  p.end();
-  return 0;
-}
-
-int cwt_match_readout(cwt_ctx* ctx, const float* corr2d, int B, int NA, int NB, float temp, const float* v, int Cv,
-                      float* weighted_v, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr2d && v && weighted_v && B >= 1 && NA >= 1 && NB >= 1 && Cv >= 1, "bad arguments");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int ldp = (int)((NB + 31) & ~31L);  // zero-padded to whole 32-deep K tiles (gemm_f32d)
-  float *pw, *vt;
-  int rc;
-  if ((rc = ws(ctx, "match.attn", (size_t)B * NA * ldp, &pw)) || (rc = ws(ctx, "match.vt", (size_t)B * Cv * ldp, &vt)))
-    return rc;
-  Prof p(ctx, st, "match_readout", 2.0 * B * NA * (double)NB * Cv, 4.0 * B * ((double)NA * NB * 2 + (double)NB * Cv));
-  if ((rc = launch_match_softmax(corr2d, B, NA, NB, temp, ldp, pw, st))) return rc;
-  if ((rc = launch_match_vt(v, B, NB, Cv, ldp, vt, st))) return rc;
-  if ((rc = readout_gemm(ctx, pw, vt, B, NA, Cv, ldp, weighted_v, st))) return rc;
-  p.end();
-  return 0;
-}
-
-int cwt_match_readout_backward(cwt_ctx* ctx, const float* corr2d, int B, int NA, int NB, float temp, const float* v,
-                               int Cv, const float* d_weighted_v, const uint8_t* ig_mask, float* d_corr2d, float* d_v,
-                               void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(corr2d && d_corr2d && B >= 1 && NA >= 1 && NB >= 1, "bad arguments");
-  CWT_CHECK(!d_weighted_v || (v && Cv >= 4 && Cv % 4 == 0), "d_weighted_v needs v and Cv % 4 == 0");
-  CWT_CHECK(!d_v || d_weighted_v, "d_v needs d_weighted_v");
-  CWT_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int ldp = (int)((NB + 31) & ~31L);
-  const long E = (long)B * NA * NB;
-  float *pw, *dA;
-  int rc;
-  if ((rc = ws(ctx, "match.attn", (size_t)B * NA * ldp, &pw)) || (rc = ws(ctx, "mb.dA", (size_t)E, &dA))) return rc;
-  Prof p(ctx, st, "match_readout_backward", 2.0 * 2.0 * B * NA * (double)NB * Cv,
-         4.0 * B * ((double)NA * NB * 4 + (double)(NA + NB) * Cv * 2));
-  if (d_weighted_v) {
-    // attn = softmax(temp corr2d) again (the forward's masked corr2d), dA = d_wv . v^T
-    if ((rc = launch_match_softmax(corr2d, B, NA, NB, temp, ldp, pw, st))) return rc;
-    for (int b = 0; b < B; ++b)
-      if ((rc = gemm_nt(ctx, d_weighted_v + (long)b * NA * Cv, v + (long)b * NB * Cv, NA, NB, Cv,
-                        dA + (long)b * NA * NB, st)))
-        return rc;
-    // d corr2d += temp P (dA - <P, dA>) (accumulating into the caller's gradient at corr2d)
-    if ((rc = launch_match_softmax_bwd(pw, ldp, dA, B * NA, NB, temp, 1, d_corr2d, st))) return rc;
-  }
-  if (ig_mask && (rc = launch_match_zero_ig_cols(d_corr2d, ig_mask, B, NA, NB, st))) return rc;
-  if (d_v) {  // d_v[b] = attn[b]^T . d_wv[b]
-    const long lda = ld32(NA);
-    float *pt, *dwt;
-    if ((rc = ws(ctx, "mb.PT", (size_t)B * ldp * lda, &pt)) || (rc = ws(ctx, "mb.dwvT", (size_t)B * Cv * lda, &dwt)))
-      return rc;
-    if ((rc = launch_match_vt(pw, B, NA, ldp, (int)lda, pt, st)) ||
-        (rc = launch_match_vt(d_weighted_v, B, NA, Cv, (int)lda, dwt, st)))
-      return rc;
-    for (int b = 0; b < B; ++b)
-      if ((rc = gemm_nt(ctx, pt + (long)b * ldp * lda, dwt + (long)b * Cv * lda, NB, Cv, (int)lda,
-                        d_v + (long)b * NB * Cv, st)))
-        return rc;
-  }
-  p.end();
-  return 0;
-}
 
 static bool wa_channels_ok(int C) { return (C >= 64 && C <= 512 && C % 64 == 0) || C == 1024 || C == 2048; }
 

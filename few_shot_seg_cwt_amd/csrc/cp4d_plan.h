@@ -269,6 +269,6 @@ constexpr int cp4d_wgrad_part_floats() {
   return std::max(std::max(WG_G_WIDE * (18 * 10 * 10 + 10), WG_G_THIN * (18 * 2 * 10 + 10)),
                   WG_G_NC * (18 * CWT_MATCH_MAX_L * 10 + 10));
 }
-static_assert(cp4d_wgrad_part_floats() == 1477120, "the weight gradient's workspace (api_heads.hip sizes it once)");
+static_assert(cp4d_wgrad_part_floats() == 1477120, "the weight gradient's workspace (match_plan.h sizes it once)");
 
 }  // namespace cwt

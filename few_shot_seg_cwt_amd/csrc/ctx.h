@@ -14,6 +14,7 @@
 #include "common.h"
 #include "extract_plan.h"
 #include "kernels.h"
+#include "match_plan.h"  // ld32, the row padding the GEMM helpers below share with the match pass's plan
 
 namespace cwt {
 
@@ -143,8 +144,6 @@ int gemm_f32d(cwt_ctx* ctx, const float* A, const float* Bm, int M, int N, int K
 int readout_gemm(cwt_ctx* ctx, const float* P, const float* vt, int B, int NA, int Cv, int ldp, float* out,
                  hipStream_t st);
 int gemm_nt(cwt_ctx* ctx, const float* A, const float* W, int M, int N, int K, float* C, hipStream_t st);
-
-static inline long ld32(long n) { return (n + 31) & ~31L; }
 
 // A zeroed ConvSArgs / ConvArgs with the conv's geometry, M and K set (down2, conv_out_size: extract_plan.h)
 template <class Args>

@@ -140,20 +140,32 @@ class NeighConsensus(torch.nn.Module):
         return ps
 
     def packed(self) -> torch.Tensor:
-        """The layers' parameters in cwt_match_corr_forward's order (cached per parameter version)."""
-        ps = []
-        for i in (0, 2, 4):
-            layer = self.conv[i]
-            if self.conv_type == "cv4":
-                ps += [layer.weight, layer.bias]
-            else:
-                ps += [layer.conv1.weight, layer.conv1.bias, layer.conv2.weight, layer.conv2.bias]
+        """param_list() as cwt_match_corr_forward's one vector (cached per parameter version)."""
+        ps = self.param_list()
         key = tuple((p.data_ptr(), p._version) for p in ps)
         if self._packed is None or key != self._packed_key:
-            with torch.no_grad():
-                self._packed = torch.cat([p.detach().reshape(-1).float() for p in ps]).contiguous()
-            self._packed_key = key
+            self._packed, self._packed_key = _pack(ps), key
         return self._packed
+
+
+def _pack(params) -> torch.Tensor:
+    """The layers' parameters as the one packed vector of the cwt_match_corr_* entries
+    (csrc/match_plan.h: match_params)."""
+    with torch.no_grad():
+        return torch.cat([p.detach().reshape(-1).float() for p in params]).contiguous()
+
+
+def _alloc_saved(B: int, L: int, h: int, w: int, symmetric, readout, dev) -> torch.Tensor:
+    """The buffer cwt_match_corr_forward_train keeps its activations in."""
+    n = C.c_int64()
+    _lib.check(_lib.lib().cwt_match_corr_saved_floats(B, L, h, w, int(symmetric), int(readout), C.byref(n)),
+               "cwt_match_corr_saved_floats")
+    return torch.empty(n.value, device=dev, dtype=torch.float32)
+
+
+def _split_grads(d_params: torch.Tensor, shapes):
+    """d_params (the packed vector's layout) as one gradient per parameter."""
+    return [g.reshape(s) for g, s in zip(torch.split(d_params, [math.prod(s) for s in shapes]), shapes)]
 
 
 class SpatialContextEncoder(torch.nn.Module):
@@ -263,12 +275,8 @@ class _MatchCorrFn(torch.autograd.Function):
         # corr [B, L, hw, hw] contiguous; vt [B, Cv, h, w] token-contiguous (channels_last) or None
         B, L = corr.shape[0], corr.shape[1]
         hw, dev = h * w, corr.device
-        with torch.no_grad():
-            packed = torch.cat([p.detach().reshape(-1).float() for p in params]).contiguous()
-        n = C.c_int64()
-        _lib.check(_lib.lib().cwt_match_corr_saved_floats(B, L, h, w, int(symmetric), int(vt is not None), C.byref(n)),
-                   "cwt_match_corr_saved_floats")
-        saved = torch.empty(n.value, device=dev, dtype=torch.float32)
+        packed = _pack(params)
+        saved = _alloc_saved(B, L, h, w, symmetric, vt is not None, dev)
         corr2d = torch.empty((B, hw, hw), device=dev, dtype=torch.float32)
         Cv = vt.shape[1] if vt is not None else 0
         wv = torch.empty((B, h, w, Cv), device=dev, dtype=torch.float32) if vt is not None else None
@@ -298,9 +306,8 @@ class _MatchCorrFn(torch.autograd.Function):
             _lib.ctx(dev.index), _lib.ptr(corr), B, L, h, w, _lib.ptr(packed), sym, temp,
             _lib.ptr(vt) if has_v else None, Cv, _lib.ptr(saved), _lib.ptr(gc), _lib.ptr(gw), _lib.ptr(d_corr),
             _lib.ptr(d_params), _lib.ptr(d_v), _lib.stream_ptr(dev)), "cwt_match_corr_backward")
-        sizes = [math.prod(s) for s in ctx.shapes]
-        grads = [g.reshape(s) for g, s in zip(torch.split(d_params, sizes), ctx.shapes)]
-        return (d_corr, d_v.permute(0, 3, 1, 2) if d_v is not None else None, None, None, None, None, *grads)
+        return (d_corr, d_v.permute(0, 3, 1, 2) if d_v is not None else None, None, None, None, None,
+                *_split_grads(d_params, ctx.shapes))
 
 
 def _needs_grad(*ts) -> bool:
@@ -321,12 +328,8 @@ class _MatchMaskedFn(torch.autograd.Function):
         B, L = corr.shape[0], corr.shape[1]
         hw, dev = h * w, corr.device
         Lb, cx, st = _lib.lib(), _lib.ctx(dev.index), _lib.stream_ptr(dev)
-        with torch.no_grad():
-            packed = torch.cat([p.detach().reshape(-1).float() for p in params]).contiguous()
-        n = C.c_int64()
-        _lib.check(Lb.cwt_match_corr_saved_floats(B, L, h, w, int(symmetric), 0, C.byref(n)),
-                   "cwt_match_corr_saved_floats")
-        saved = torch.empty(n.value, device=dev, dtype=torch.float32)
+        packed = _pack(params)
+        saved = _alloc_saved(B, L, h, w, symmetric, False, dev)
         corr2d = torch.empty((B, hw, hw), device=dev, dtype=torch.float32)
         _lib.check(Lb.cwt_match_corr_forward_train(cx, _lib.ptr(corr), B, L, h, w, _lib.ptr(packed), int(symmetric),
                                                    float(temp), None, 0, _lib.ptr(corr2d), None, _lib.ptr(saved), st),
@@ -369,10 +372,8 @@ class _MatchMaskedFn(torch.autograd.Function):
         _lib.check(Lb.cwt_match_corr_backward(cx, _lib.ptr(corr), B, L, h, w, _lib.ptr(packed), sym, temp, None, 0,
                                               _lib.ptr(saved), _lib.ptr(d2), None, _lib.ptr(d_corr),
                                               _lib.ptr(d_params), None, st), "cwt_match_corr_backward")
-        sizes = [math.prod(s) for s in ctx.shapes]
-        grads = [g.reshape(s) for g, s in zip(torch.split(d_params, sizes), ctx.shapes)]
         return (d_corr, d_v.permute(0, 3, 1, 2) if d_v is not None else None, None, None, None, None, None, None,
-                None, None, *grads)
+                None, None, *_split_grads(d_params, ctx.shapes))
 
 
 class MatchNet(torch.nn.Module):
@@ -399,28 +400,26 @@ class MatchNet(torch.nn.Module):
         B, L = corr.shape[0], corr.shape[1]
         if L != self.in_channel:
             raise ValueError("input corr channel inconsistent with in_channel of NCNet")
-        hw = h * w
-        nc = self.NeighConsensus
+        hw, nc = h * w, self.NeighConsensus
         # the backward is built for CenterPivotConv4d ('red') layers, the layers every config trains;
         # 'cv4' runs the inference kernels and its outputs carry no gradient
-        if nc.conv_type == "red" and _needs_grad(corr, v, *nc.param_list()):
-            vt = as_tokens(v if v.dim() == 4 else v.reshape(v.shape[0], v.shape[1], h, w)) if v is not None else None
+        train = nc.conv_type == "red" and _needs_grad(corr, v, *nc.param_list())
+        # packed ahead of the token view, as always: the order of torch's own cat and copy kernels is part of
+        # the recorded launch sequence (profiles/r10); under autograd _MatchCorrFn packs them itself, after it
+        params = None if train else nc.packed()
+        vt = as_tokens(v if v.dim() == 4 else v.reshape(v.shape[0], v.shape[1], h, w)) if v is not None else None
+        if train:
             corr2d, wv = _MatchCorrFn.apply(corr.contiguous(), vt, nc.symmetric_mode, float(self.temp), h, w,
                                             *nc.param_list())
             return corr2d, (wv if v is not None else None)
-        params = nc.packed()
         corr2d = torch.empty((B, hw, hw), device=corr.device, dtype=torch.float32)
-        wv, vt, Cv = None, None, 0
-        if v is not None:
-            vt = as_tokens(v if v.dim() == 4 else v.reshape(v.shape[0], v.shape[1], h, w))
-            Cv = vt.shape[1]
-            wv = torch.empty((B, h, w, Cv), device=corr.device, dtype=torch.float32)
-        entry = "cwt_match_corr_forward_cv4" if self.NeighConsensus.conv_type == "cv4" else "cwt_match_corr_forward"
+        Cv = vt.shape[1] if vt is not None else 0
+        wv = torch.empty((B, h, w, Cv), device=corr.device, dtype=torch.float32) if vt is not None else None
+        entry = "cwt_match_corr_forward_cv4" if nc.conv_type == "cv4" else "cwt_match_corr_forward"
         _lib.check(getattr(_lib.lib(), entry)(
-            _lib.ctx(corr.device.index), _lib.ptr(corr), B, L, h, w, _lib.ptr(params),
-            1 if self.NeighConsensus.symmetric_mode else 0, float(self.temp),
-            _lib.ptr(vt) if vt is not None else None, Cv, _lib.ptr(corr2d), _lib.ptr(wv) if wv is not None else None,
-            _lib.stream_ptr(corr.device)), entry)
+            _lib.ctx(corr.device.index), _lib.ptr(corr), B, L, h, w, _lib.ptr(params), int(bool(nc.symmetric_mode)),
+            float(self.temp), _lib.ptr(vt) if vt is not None else None, Cv, _lib.ptr(corr2d),
+            _lib.ptr(wv) if wv is not None else None, _lib.stream_ptr(corr.device)), entry)
         return corr2d, (wv.permute(0, 3, 1, 2) if wv is not None else None)
 
     def run_match_model(self, corr4d: torch.Tensor) -> torch.Tensor:

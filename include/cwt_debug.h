@@ -176,6 +176,27 @@ int cwt_debug_cp4d_plan(int dir, int B, int hA, int wA, int hB, int wB, int cin,
 int cwt_debug_cp4d_form(int form, char* buf, int64_t cap);
 int cwt_debug_cp4d_wgrad_part_floats(void);
 
+/* The match pass's plan (csrc/match_plan.h), on the host alone (no context, no device call; the
+ * CWT_MM_FUSE and CWT_MATCH_BRANCH_STREAMS knobs are read from the environment as every call reads
+ * them).  dir 0: the MatchPlan of cwt_match_corr_forward (cv4: of _forward_cv4; train: of
+ * _forward_train) with or without the readout (weighted_v); dir 1: the MatchBwdPlan of
+ * cwt_match_corr_backward producing d_corr / d_v (want_d_corr, want_d_v) with or without
+ * d_weighted_v (readout); cv4 and train are ignored there.  buf (cap bytes, NUL-terminated;
+ * CWT_EARG if too small) receives tab-separated lines:
+ *   "plan\tfwd\tmm1=direct|planar2|clast\tlayers=cp4d|cv4d\tbranches=N\tfork=0|1\tmm2=plain|add|sum\t
+ *    readout=0|1\ttrain=0|1", or "plan\tbwd\tbranches=N\td_corr=0|1\td_v=0|1\treadout=0|1\tclast=0|1";
+ *   "param\tlayer\tname\toffset\tfloats" per entry of the packed parameter vector in its order (name
+ *    conv1.weight, conv1.bias, conv2.weight, conv2.bias, or weight, bias for cv4), then
+ *    "param\ttotal\tfloats"; for the 'red' layers "role\tbranch\tlayer\tWa\tba\tWb\tbb": the offsets of
+ *    the filters and biases that branch applies over the a and the b positions;
+ *   "buf\ttensor\twhere\toffset\tfloats\tper": where is a workspace's name (offset 0) or "saved" (the
+ *    float offset into the caller's buffer), per is "Cv" where floats counts one value channel, else
+ *    "1"; a tensor the pass does not have is left out; then, training forward and backward,
+ *    "saved\ttotal\tfloats" (= cwt_match_corr_saved_floats).
+ * Returns the plan's rc: 0, or CWT_EARG with the entry point's message for a refused call. */
+int cwt_debug_match_plan(int dir, int B, int L, int h, int w, int symmetric, int cv4, int train, int readout,
+                         int want_d_corr, int want_d_v, char* buf, int64_t cap);
+
 /* Timing-study hook of cwt_episode_tail: with CWT_TAIL_STAMPS=1 in the environment the tail runs a
  * separately compiled instantiation whose workgroups record s_memtime at each phase edge
  * ([G][16]: 0 entry, 2k-1 / 2k before / after grid barrier k, 11 the partials written, 14 / 15

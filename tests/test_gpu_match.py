@@ -67,6 +67,86 @@ def test_corr_forward(dev, B, L, h, w, sym):
     assert max(errs.values()) < TOL, errs
 
 
+# The paths behind the two knobs of the match pass's plan (csrc/match_plan.h), changed inside one
+# process: test_corr_forward's two symmetric shapes, ragged against the MutualMatching kernels' 8-row
+# blocks and 64-column tiles.  Inference (no_grad: cwt_match_corr_forward) under CWT_MM_FUSE=1 takes
+# launch_mutual_matching_planar2 and launch_mutual_matching_sum at (2, 2, 9, 13) and the sum alone at
+# (1, 1, 12, 12); under CWT_MATCH_BRANCH_STREAMS=0 branch 1 runs after branch 0 through the same two
+# buffers.  The training forward (grad enabled: cwt_match_corr_forward_train) keeps the add and takes
+# planar2 alone.  Each case first holds the plan of its call to the path it is there for.
+KNOB_SHAPES = [(2, 2, 9, 13), (1, 1, 12, 12)]
+KNOB_MODES = pytest.mark.parametrize("grad", [False, True], ids=["infer", "train"])
+_knob_cases = {}
+
+
+def _knob_run(net, corr, v, grad):
+    with torch.set_grad_enabled(grad):
+        corr2d, wv = net.corr_forward(corr, v, ret_attn=True)
+    torch.cuda.synchronize()
+    assert corr2d.requires_grad == grad   # the parameters require grad: grad mode alone picks the entry point
+    return corr2d.detach(), wv.detach()
+
+
+def _knob_case(dev, B, L, h, w):
+    """test_corr_forward's inputs at a shape, the default runs' outputs (inference, training) and the
+    oracle's, once per shape"""
+    key = (B, L, h, w)
+    if key not in _knob_cases:
+        from oracle import match_oracle as M
+        net = _net(dev, L, True, 20.0, seed=11 + L)
+        corr = _corr(dev, B, L, h, w, seed=5 * h + w)
+        v = torch.rand(B, 64, h, w, generator=torch.Generator().manual_seed(13)).to(dev)
+        layers = M.layers_from_state({k: t.cpu() for k, t in net.state_dict().items()})
+        ref = M.corr_forward(corr.double().cpu(), v.double().cpu(), layers, 20.0, True)
+        default = {grad: _knob_run(net, corr, v, grad) for grad in (False, True)}
+        _knob_cases[key] = (net, corr, v, default, ref)
+    return _knob_cases[key]
+
+
+def _knob_plan(B, L, h, w, grad):
+    """the decisions of the call's MatchPlan under the environment as it is (cwt_debug_match_plan)"""
+    import ctypes
+    from few_shot_seg_cwt_amd import _lib
+    buf = ctypes.create_string_buffer(1 << 14)
+    _lib.check(_lib.lib().cwt_debug_match_plan(0, B, L, h, w, 1, 0, int(grad), 1, 0, 0, buf, len(buf)),
+               "cwt_debug_match_plan")
+    return dict(kv.split("=") for kv in buf.value.decode().splitlines()[0].split("\t")[2:])
+
+
+@KNOB_MODES
+@pytest.mark.parametrize("B,L,h,w", KNOB_SHAPES)
+def test_corr_forward_one_stream(dev, monkeypatch, B, L, h, w, grad):
+    """CWT_MATCH_BRANCH_STREAMS=0: the same kernels on the same inputs, one branch after the other."""
+    monkeypatch.delenv("CWT_MM_FUSE", raising=False)
+    monkeypatch.delenv("CWT_MATCH_BRANCH_STREAMS", raising=False)
+    net, corr, v, default, _ = _knob_case(dev, B, L, h, w)
+    assert _knob_plan(B, L, h, w, grad)["fork"] == "1"
+    monkeypatch.setenv("CWT_MATCH_BRANCH_STREAMS", "0")
+    p = _knob_plan(B, L, h, w, grad)
+    assert (p["fork"], p["branches"], p["train"]) == ("0", "2", str(int(grad)))
+    corr2d, wv = _knob_run(net, corr, v, grad)
+    assert torch.equal(corr2d, default[grad][0]) and torch.equal(wv, default[grad][1])
+
+
+@KNOB_MODES
+@pytest.mark.parametrize("B,L,h,w", KNOB_SHAPES)
+def test_corr_forward_fused(dev, monkeypatch, B, L, h, w, grad):
+    """CWT_MM_FUSE=1 at test_corr_forward's bar against its reference."""
+    monkeypatch.delenv("CWT_MM_FUSE", raising=False)
+    monkeypatch.delenv("CWT_MATCH_BRANCH_STREAMS", raising=False)
+    net, corr, v, default, (c2o, wvo) = _knob_case(dev, B, L, h, w)
+    monkeypatch.setenv("CWT_MM_FUSE", "1")
+    p = _knob_plan(B, L, h, w, grad)
+    assert (p["mm1"], p["mm2"], p["train"]) == ("planar2" if L == 2 else "direct", "add" if grad else "sum",
+                                                str(int(grad)))
+    corr2d, wv = _knob_run(net, corr, v, grad)
+    errs = dict(corr2d=rel(corr2d, c2o), weighted_v=rel(wv, wvo))
+    same = torch.equal(corr2d, default[grad][0]) and torch.equal(wv, default[grad][1])
+    print(f"corr_forward fused B={B} L={L} {h}x{w} grad={grad} mm1={p['mm1']} mm2={p['mm2']}: {errs}, "
+          f"bitwise equal to the default: {same}")
+    assert max(errs.values()) < TOL, errs
+
+
 def test_forward_from_features_and_state_dict_keys(dev):
     """MatchNet.forward (match.py:103-140): get_corr of the features -> run_match_model ->
     softmax -> bmm; the module's state_dict carries the reference's key names."""
