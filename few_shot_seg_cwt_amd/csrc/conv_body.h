@@ -146,7 +146,18 @@ __device__ __forceinline__ void split3_bf16(const f32x4& x0, const f32x4& x1, bf
 // PF bits: 1 fragment prefetch; 2 / 4 timing studies (no MFMAs / no operand DMA); 8 buffer
 // addressing of the operand DMA (every production instantiation sets it); 16 timing study of the
 // x6 WN = 128 forms without the A split (wrong numbers, same data movement and MFMAs); 32 timing
-// study without the epilogue; 64 timing study: every workgroup returns at once (the launch alone).
+// study without the epilogue; 64 timing study: every workgroup returns at once (the launch alone);
+// 128 a second A source (below); 256 the GEMM-shaped launch (x6, with PF & 8: kh = kw = 1, pad = 0,
+// whatever the stride, batched or not, one A source or two).  There every A piece's image geometry
+// is constant over K: a row is inside the image for every K-tile or past M for every K-tile, and
+// the K offset is i_kt * 128 as it is for B.  So a_roff[j] carries the row's whole constant offset
+// (the past-M sentinel folded in once), the K-tile offset rides in the uniform soffset, and the loop
+// holds no tap walk, no compare and no select; pieces, ring, waits, barriers, fragment reads, MFMA
+// order and epilogue are the general path's, and so are the output bits.  With stride 1 over the
+// whole image (Hi == Ho, Wi == Wo) row m's pixel is m: no division in the prologue.  In the 4x1
+// layouts a wave whose rows are all past M keeps issuing its DMA pieces, waits and barriers but
+// reads no fragments, splits nothing, multiplies nothing and stores nothing (its rows have no
+// output).
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTG, int PREC, int PF>
 __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
   static_assert(PREC == 0 || PREC == 1 || PREC == 3 || PREC == 6,
@@ -199,14 +210,29 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
   // ---- LDS-DMA source geometry (constant over K) ----
   const int lrow = lane >> 3, lslot = lane & 7;
   const int cblocks = a.Ci >> (PREC == 1 ? 6 : 5);  // 128-B lines per pixel
+  constexpr bool GEMM = (PF & 256) != 0;
+  static_assert(!GEMM || (PREC == 6 && (PF & 8) != 0), "GEMM-shaped path: x6 with buffer addressing");
   int a_ih0[LA], a_iw0[LA], a_pix0[LA], a_ch[LA];
   const int HoWo = a.Ho * a.Wo;
+  // GEMM: the pixel of output row m in an [N][H][W] source read at `stride` (pad 0); a source of the
+  // output's own height and width read at stride 1 has row m at pixel m
+  auto gemm_pix = [&](int m, int H, int W, int stride) {
+    if (stride == 1 && W == a.Wo && H == a.Ho) return m;
+    const int n = m / HoWo, rem = m - n * HoWo;
+    const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
+    return (n * H + oh * stride) * W + ow * stride;
+  };
+  // GEMM, 4x1 layouts: this wave's rows are all past M (wave-uniform)
+  const bool idle = GEMM && WAVES_N == 1 && m0 + wm * WM >= a.M;
 #pragma unroll
   for (int j = 0; j < LA; ++j) {
     const int r = (wv * LA + j) * 8 + lrow;
     a_ch[j] = (lslot ^ ((r >> 1) & 7)) * 8;
     const int m = m0 + r;
-    if (m < a.M) {
+    if constexpr (GEMM) {
+      a_pix0[j] = m < a.M ? gemm_pix(m, a.Hi, a.Wi, a.stride) : -1;  // -1: past M (a_roff's sentinel below)
+      a_ih0[j] = a_iw0[j] = 0;
+    } else if (m < a.M) {
       const int n = m / HoWo;
       const int rem = m - n * HoWo;
       const int oh = rem / a.Wo;
@@ -258,9 +284,14 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
 #pragma unroll
     for (int j = 0; j < LA; ++j) {
       const int m = m0 + (wv * LA + j) * 8 + lrow;
-      const int n = m / HoWo, rem = m - n * HoWo;
-      const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
-      const int pix2 = (n * a.Hi2 + oh * a.stride2) * a.Wi2 + ow * a.stride2;
+      int pix2;
+      if constexpr (GEMM) {
+        pix2 = gemm_pix(m, a.Hi2, a.Wi2, a.stride2);
+      } else {
+        const int n = m / HoWo, rem = m - n * HoWo;
+        const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
+        pix2 = (n * a.Hi2 + oh * a.stride2) * a.Wi2 + ow * a.stride2;
+      }
       a_roff2[j] = m < a.M ? (pix2 * cbl2 * 64 + a_ch[j]) * 2 : (int)0x80000000;  // rows past M read zeros
     }
   }
@@ -270,7 +301,8 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
     rsA = __builtin_amdgcn_make_buffer_rsrc((void*)xs_b, (short)0, (int)a_bytes, 0x00020000);
     rsB = __builtin_amdgcn_make_buffer_rsrc((void*)ws_b, (short)0, (int)((long)a.Co * a.ktiles_total * 128), 0x00020000);
 #pragma unroll
-    for (int j = 0; j < LA; ++j) a_roff[j] = (a_pix0[j] * cbl * 64 + a_ch[j]) * 2;
+    for (int j = 0; j < LA; ++j)
+      a_roff[j] = GEMM && a_pix0[j] < 0 ? (int)0x80000000 : (a_pix0[j] * cbl * 64 + a_ch[j]) * 2;
 #pragma unroll
     for (int j = 0; j < LB; ++j) b_voff[j] = b_off[j] * 2;
     if constexpr (PREC == 6) {
@@ -291,7 +323,34 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
     if (PF & 4) return;  // timing study: no operand traffic
     char* sb = smem + stg * STG_BYTES;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr ((PF & 8) != 0) {
+    if constexpr (GEMM) {  // no tap walk, no per-piece compare or select: a_roff[j] + the K-tile's soffset
+      bool second = false;  // uniform: the tile's source
+      if constexpr (DUAL) {
+        second = i_kt >= a.kt_switch;
+        if (second) {
+#pragma unroll
+          for (int j = 0; j < LA; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA2, (CWT_LDS void*)(sb + (wv * LA + j) * 1024), 16, a_roff2[j],
+                                                     (i_kt - a.kt_switch) * 128, 0, 0);
+        }
+      }
+      if (!second) {
+#pragma unroll
+        for (int j = 0; j < LA; ++j)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (CWT_LDS void*)(sb + (wv * LA + j) * 1024), 16, a_roff[j],
+                                                   i_kt * 128, 0, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < LB; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (CWT_LDS void*)(sb + BM * 128 + (wv * LB + j) * 1024), 16,
+                                                 b_voff[j], i_kt * 128, 0, 0);
+#pragma unroll
+      for (int j = 0; j < LBL; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, (CWT_LDS void*)(sb + LO_OFF + ((wv * LBL + j) % NLO) * 1024), 16,
+                                                 l_voff[j], i_kt * 64, 0, 0);
+      ++i_kt;
+      return;
+    } else if constexpr ((PF & 8) != 0) {
       const int dy = i_ky * a.dil, dx = i_kx * a.dil;
       const int uni = ((dy * a.Wi + dx) * cblocks + i_cb) * 128;
       bool second = false;  // uniform: the tile's source
@@ -483,18 +542,27 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
     }
   };
 
+  static_assert(!GEMM || (PF & 1) == 0, "GEMM-shaped path: the forms without fragment prefetch");
   if constexpr ((PF & 1) == 0) {
 #pragma unroll
     for (int s = 0; s < NSTG - 1; ++s)
       if (s < T) issue(s);
 
-    for (int t = 0; t < T; ++t) {
+    // publish tile t, refill the slot tile t - 1 occupied
+    auto ring_step = [&](int t) {
       wait_tiles<LPT>(min(NSTG - 2, T - 1 - t));
       block_sync_lds();
       if (t + NSTG - 1 < T) issue((t + NSTG - 1) % NSTG);
-      Frags F;
-      read_frags(F, t % NSTG);
-      mfmas(F, t % NSTG);
+    };
+    if (idle) {  // a loop of its own: the working waves' loop holds no branch on it
+      for (int t = 0; t < T; ++t) ring_step(t);
+    } else {
+      for (int t = 0; t < T; ++t) {
+        ring_step(t);
+        Frags F;
+        read_frags(F, t % NSTG);
+        mfmas(F, t % NSTG);
+      }
     }
   } else {
     // prologue: tiles 0 .. NSTG-1 fill every slot; tile 0's fragments
@@ -534,6 +602,7 @@ __device__ __forceinline__ void conv_s_body(const ConvSArgs& a) {
     return;
   }
   block_sync_lds();
+  if (idle) return;  // no barrier below this one; the wave's rows have no output
   float* ep = (float*)smem + wv * (EP_ROWS * EP_LD);
   constexpr int LPR = WN / 8;    // lanes per output row (8 channels each)
   constexpr int RPR = 64 / LPR;  // rows per round

@@ -13,9 +13,12 @@ namespace cwt {
 
 // X(bm, bn, var, WAVES_M, WAVES_N, NSTG, PF, FIXED): the form conv_igemm_*<bm, bn, WAVES_M, WAVES_N,
 //   NSTG, STAGE, PF> (block = WAVES_M * WAVES_N * 64 threads; NSTG the LDS ring's depth; PF the
-//   body's main-loop bits, conv_body.h).  FIXED = 1: a timing-study form that carries its own tile --
-//   the debug entry points replace whatever tile is named beside its var with the row's (the grid
-//   must be the kernel's), and x3s / b16 / f32d build it at STAGE 0 only.
+//   body's main-loop bits, conv_body.h: 1 prefetch, 2 / 4 / 16 / 32 / 64 timing studies, 128 two A
+//   sources; 8 (buffer addressing) is set by every kernel, 256 (the GEMM-shaped path) by the x6
+//   launcher for the rows of CWT_CONV_GEMM_ROWS_X6 below -- neither appears in a row).  FIXED = 1:
+//   a timing-study form that carries its own tile -- the debug entry points replace whatever tile
+//   is named beside its var with the row's (the grid must be the kernel's), and x3s / b16 / f32d
+//   build it at STAGE 0 only.
 // A(bm, bn, var, target): var on this tile launches the same tile's row `target`.
 //
 // All four families.  var 0 the base loop; 1 fragment prefetch, same waves; 2 prefetch with 8 waves
@@ -64,6 +67,26 @@ namespace cwt {
 
 constexpr int kConvDualVar = 20;
 
+// conv_igemm_x6 only: G(bm, bn, var) names a row above that also exists with PF bit 256, the
+// GEMM-shaped path of conv_body.h.  The x6 launcher (conv_x6.hip), not the plan tables, takes it
+// for a launch with kh == kw == 1 && pad == 0 -- every 1x1 conv, the two-source forms and the
+// Winograd products -- unless CWT_X6_GEMM_BODY=0; a row not listed here runs its general form.
+// The rows are those the 473^2 x 2 plan table (conv_plans_x6.inc) takes on such launches, each kept
+// because no table shape ran slower on it than on the general body (profiles/r11/sweeps): var 3 / 4
+// / 5 and the dual 24 / 25 on their tiles and the base 64x64.  The base 256x256 and 128x256 rows of
+// the 473^2 x 4 and 641^2 tables have no GEMM-shaped body: not measured.
+#define CWT_CONV_GEMM_ROWS_X6(G)                                                               \
+  G(128, 128, 3) G(64, 64, 3) G(128, 128, 4) G(128, 128, 5) G(128, 64, 5) G(64, 128, 5)        \
+  G(128, 128, 24) G(128, 128, 25) G(128, 64, 25) G(64, 128, 25) G(64, 64, 0)
+
+constexpr bool x6_gemm_row(int bm, int bn, int var) {
+#define CWT_G(BM, BN, VAR) \
+  if (bm == BM && bn == BN && var == VAR) return true;
+  CWT_CONV_GEMM_ROWS_X6(CWT_G)
+#undef CWT_G
+  return false;
+}
+
 struct ConvForm {
   int bm, bn, var, waves_m, waves_n, nstg, pf;
   bool fixed_tile;
@@ -88,12 +111,17 @@ void with_stage(int stage, F&& f) {
 
 // Launch the row p names directly (aliases already resolved: find_conv_form).  Fam::launch<BM, BN,
 // WAVES_M, WAVES_N, NSTG, STAGE, PF>(a, grid, st) launches the family's kernel; Fam::kX6 adds the
-// x6-only rows, Fam::kStudyStage0 builds the FIXED rows at STAGE 0 only.
+// x6-only rows, Fam::kStudyStage0 builds the FIXED rows at STAGE 0 only.  gemm (x6 only): a row of
+// CWT_CONV_GEMM_ROWS_X6 launches its GEMM-shaped body (PF | 256), any other row its own.
 template <class Fam, int STAGE>
-void launch_form(const ConvPlan& p, const ConvSArgs& a, dim3 grid, hipStream_t st) {
-#define CWT_ROW(BM, BN, VAR, WM, WN, NS, PF, FIXED)     \
-  if (p.bm == BM && p.bn == BN && p.var == VAR)         \
-    return Fam::template launch<BM, BN, WM, WN, NS, (FIXED && Fam::kStudyStage0) ? 0 : STAGE, PF>(a, grid, st);
+void launch_form(const ConvPlan& p, const ConvSArgs& a, dim3 grid, hipStream_t st, bool gemm = false) {
+#define CWT_ROW(BM, BN, VAR, WM, WN, NS, PF, FIXED)                                            \
+  if (p.bm == BM && p.bn == BN && p.var == VAR) {                                              \
+    constexpr int S = (FIXED && Fam::kStudyStage0) ? 0 : STAGE;                                \
+    if constexpr (Fam::kX6 && x6_gemm_row(BM, BN, VAR))                                        \
+      if (gemm) return Fam::template launch<BM, BN, WM, WN, NS, S, (PF) | 256>(a, grid, st);   \
+    return Fam::template launch<BM, BN, WM, WN, NS, S, PF>(a, grid, st);                       \
+  }
 #define CWT_ALIAS(BM, BN, VAR, TARGET)
   CWT_CONV_FORMS(CWT_ROW, CWT_ALIAS)
   if constexpr (Fam::kX6) {

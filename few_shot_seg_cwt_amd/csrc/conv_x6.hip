@@ -66,8 +66,19 @@ int launch_occupy(int nwg, int us, hipStream_t st) {
 // conv_forms.h.  p names a row directly (launch_conv_x3s has resolved it).
 CWT_CONV_FAMILY(FamX6, conv_igemm_x6, true, false);
 
+// A GEMM-shaped launch (kh = kw = 1, pad = 0: every K-tile reads the same pixels) takes its row's
+// GEMM body (PF bit 256, conv_body.h) where the row has one (CWT_CONV_GEMM_ROWS_X6).
+// CWT_X6_GEMM_BODY=0 keeps the general body: the A/B switch, read at every launch so that one
+// process can run both.
+static bool x6_gemm_body(const ConvSArgs& a) {
+  if (a.kh != 1 || a.kw != 1 || a.pad != 0) return false;
+  const char* v = getenv("CWT_X6_GEMM_BODY");
+  return !(v && v[0] == '0');
+}
+
 void launch_tiles_x6(int stage, const ConvSArgs& a, const ConvPlan& p, dim3 grid, hipStream_t st) {
-  with_stage<8>(stage, [&](auto s) { launch_form<FamX6, decltype(s)::value>(p, a, grid, st); });
+  const bool gemm = x6_gemm_body(a);
+  with_stage<8>(stage, [&](auto s) { launch_form<FamX6, decltype(s)::value>(p, a, grid, st, gemm); });
 }
 
 }  // namespace cwt

@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--occupy", type=int, default=0, help="CUs held meanwhile (the pipeline's resident inner loop: 59)")
     ap.add_argument("--out", default="conv_dual_sweep.json")
+    ap.add_argument("--ab", default="", help="an environment knob read at every launch (CWT_X6_GEMM_BODY): time the "
+                    "library's own plan with it at 0 and at 1, alternating in this process")
+    ap.add_argument("--pairs", type=int, default=5, help="--ab: timings per arm")
     args = ap.parse_args()
     css.OCCUPY = args.occupy
     layers, S, N = (int(v) for v in args.config.split(":"))
@@ -62,6 +65,14 @@ def main():
                 ctx, _lib.ptr(t), N, Ho, Ho, K1, _lib.ptr(x), H, H, K2, stride, _lib.ptr(w3), _lib.ptr(one),
                 _lib.ptr(zero), _lib.ptr(wd), _lib.ptr(one), _lib.ptr(zero), Co, 1, _lib.ptr(y), bm, bn, ns, sp))
 
+        if args.ab:
+            tm = css.ab_timed(dual(0, 0, 0), args.reps, args.ab, args.pairs)
+            m0, m1, gain, spread = css.ab_summary(tm)
+            print(f"{name} M={M} Co={Co} K={K1}+{K2}: {args.ab}=0 {m0:.1f}  =1 {m1:.1f} us  gain {gain:+.1f} %  "
+                  f"(repeat spread {spread:.1f} %)", flush=True)
+            res.append({"name": name, "M": M, "Co": Co, "K1": K1, "K2": K2, "knob": args.ab, "us": tm,
+                        "gain_pct": round(gain, 2), "spread_pct": round(spread, 2)})
+            continue
         rows = []
         for bm, bn in [(0, 0)] + FORMS:
             for ns in (0,) if bm == 0 else (1, 2, 4):

@@ -100,7 +100,32 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-def sweep(layers, size, n_img, reps, quick, prec=3, variants=(0,), only=None):
+def ab_timed(fn, reps, env, pairs):
+    """The same call with the environment knob `env` at 0 and at 1 (a knob the library reads at every
+    launch), alternating, `pairs` times each: {"0": [us, ...], "1": [us, ...]}"""
+    saved, out = os.environ.get(env), {"0": [], "1": []}
+    try:
+        for _ in range(pairs):
+            for v in ("0", "1"):
+                os.environ[env] = v
+                out[v].append(round(timed(fn, reps), 2))
+    finally:
+        if saved is None:
+            os.environ.pop(env, None)
+        else:
+            os.environ[env] = saved
+    return out
+
+
+def ab_summary(t):
+    """min of each arm, the gain of arm 1 in percent of arm 0, and the larger arm's (max - min) / min
+    in percent: the sweep's own repeat spread"""
+    m0, m1 = min(t["0"]), min(t["1"])
+    spread = max((max(v) - min(v)) / min(v) for v in t.values()) * 100.0
+    return m0, m1, (m0 - m1) / m0 * 100.0, spread
+
+
+def sweep(layers, size, n_img, reps, quick, prec=3, variants=(0,), only=None, ab=None, pairs=5):
     print(f"== R{layers} S={size} N={n_img}", flush=True)
     dev = torch.device("cuda", 0)
     lib, ctx, sp = _lib.lib(), _lib.ctx(0), _lib.stream_ptr()
@@ -157,6 +182,18 @@ def sweep(layers, size, n_img, reps, quick, prec=3, variants=(0,), only=None):
                 ctx, _lib.ptr(xs), n_img, Hi, Hi, Ci, _lib.ptr(ws), _lib.ptr(sc), _lib.ptr(sh), Co, k, stride, pad,
                 dil, None, Co, _lib.ptr(rs), 1, None, Co, 0, _lib.ptr(ys), bm, bn, ns, sp))
 
+        if ab:   # the library's own plan, knob off against knob on
+            t = ab_timed(new(0, 0, 0), reps, ab, pairs)
+            m0, m1, gain, spread = ab_summary(t)
+            print(f"{name:10s} x{cnt:2d} {Ci:4d}->{Co:4d} k{k} s{stride} @{Ho:3d} M={n_img * Ho * Ho:6d} K={Ci * k * k:6d}: "
+                  f"{ab}=0 {m0:7.1f}  =1 {m1:7.1f} us  gain {gain:+5.1f} %  (repeat spread {spread:.1f} %)", flush=True)
+            res_all.append({"cfg": f"{layers}:{size}:{n_img}", "prec": prec, "name": name, "count": cnt, "Ci": Ci,
+                            "Co": Co, "k": k, "stride": stride, "dil": dil, "Ho": Ho, "knob": ab, "us": t,
+                            "gain_pct": round(gain, 2), "spread_pct": round(spread, 2)})
+            tot_auto += cnt * m0
+            tot_best += cnt * m1
+            del x, w, wp, xs, ws, r, rs, y, ys
+            continue
         t_auto = timed(new(0, 0, 0), reps)
         rows = []
         if not quick:
@@ -201,7 +238,8 @@ def sweep(layers, size, n_img, reps, quick, prec=3, variants=(0,), only=None):
                         "Ho": Ho, "M": M, "K": K, "batch": batch, "stride": stride, "dil": dil, "res": has_res,
                         "auto_us": round(t_auto, 2), "plans": rows})
         del x, w, wp, xs, ws, r, rs, y, ys
-    print(f"sum over the stack: auto {tot_auto:.1f} us, best {tot_best:.1f} us", flush=True)
+    print(f"sum over the stack: {'knob 0' if ab else 'auto'} {tot_auto:.1f} us, {'knob 1' if ab else 'best'} {tot_best:.1f} us",
+          flush=True)
     torch.cuda.empty_cache()
     return res_all
 
@@ -221,6 +259,9 @@ def main():
     ap.add_argument("--only", default="", help="comma list of shape names (default: all)")
     ap.add_argument("--occupy", type=int, default=0,
                     help="time every plan while this many CUs are held (the pipeline's resident inner loop: 59)")
+    ap.add_argument("--ab", default="", help="an environment knob the library reads at every launch (CWT_X6_GEMM_BODY): "
+                    "time each shape's own plan with it at 0 and at 1, alternating in this process")
+    ap.add_argument("--pairs", type=int, default=5, help="--ab: timings per arm")
     args = ap.parse_args()
     global OCCUPY
     OCCUPY = args.occupy
@@ -229,7 +270,8 @@ def main():
     for cfg in args.configs.split(","):
         L, S, N = (int(v) for v in cfg.split(":"))
         res_all += sweep(L, S, N, args.reps, args.quick, args.prec,
-                         tuple(int(v) for v in args.vars.split(",")), set(filter(None, args.only.split(","))))
+                         tuple(int(v) for v in args.vars.split(",")), set(filter(None, args.only.split(","))),
+                         args.ab or None, args.pairs)
         with open(os.path.join(ROOT, "gpurun_out", args.out), "w") as f:
             json.dump(res_all, f, indent=1)
 

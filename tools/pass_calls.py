@@ -85,6 +85,8 @@ for _, ks in passes[warm:]:
 res = {lab: round(sum(v) / len(v), 2) for lab, v in acc.items()}
 tot = {k: round(sum(v for lab, v in res.items() if sel(lab)), 1) for k, sel in
        [("conv", lambda s: not s.endswith(("epilogue", "wino_in", "wino_out", "maxpool"))),
+        # the launches that are plain GEMMs (kh = kw = 1, pad = 0): 1x1 convs and the Winograd products
+        ("conv_gemm_shaped", lambda s: s.endswith((".c1", ".c3", ".c3+down", ".down", ".c2.gemm"))),
         ("epilogue", lambda s: s.endswith("epilogue")), ("wino_in", lambda s: s.endswith("wino_in")),
         ("wino_out", lambda s: s.endswith("wino_out"))]}
 print("  passes used", used, "per-pass sums (us), the bottleneck conv and the PPM not included:", tot)
