@@ -125,6 +125,8 @@ SIGNATURES = {
                                 _P, _I, _I, _I, _P]),
     "cwt_debug_cp4d_layer": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "cwt_debug_cp4d_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
+    "cwt_debug_cp4d_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "cwt_debug_mutual_matching_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cwt_debug_cp4d_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "cwt_debug_cp4d_form": (_I, [_I, C.c_char_p, _I64]),
     "cwt_debug_cp4d_wgrad_part_floats": (_I, []),

@@ -598,6 +598,32 @@ int cwt_debug_cp4d_dgrad(cwt_ctx* ctx, const float* g, int B, int hA, int wA, in
   return launch_cp4d_dgrad(g, B, hA, wA, hB, wB, gin, gout, Wa, Wb, dx, accum, (hipStream_t)stream, variant);
 }
 
+// the layer's weight and bias gradients, added into dWa / dWb [cout][cin][3][3] and db1 / db2 [cout]
+// (launch_cp4d_wgrad: the form cp4d_plan_wgrad names under the environment at this call)
+int cwt_debug_cp4d_wgrad(cwt_ctx* ctx, const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin,
+                         int cout, float* dWa, float* dWb, float* db1, float* db2, void* stream) {
+  if (!ctx || !x || !gm || !dWa || !dWb || !db1 || !db2) return fail(CWT_EARG, "null argument");
+  if (B < 1 || hA < 1 || wA < 1 || hB < 1 || wB < 1) return fail(CWT_EARG, "bad shape");
+  CWT_HIP(hipSetDevice(ctx->device));
+  float* part;
+  int rc;
+  if ((rc = ws(ctx, "mb.part", (size_t)cp4d_wgrad_part_floats(), &part))) return rc;
+  return launch_cp4d_wgrad(x, gm, B, hA, wA, hB, wB, cin, cout, part, (size_t)cp4d_wgrad_part_floats(), dWa, dWb, db1,
+                           db2, (hipStream_t)stream);
+}
+
+// MutualMatching's backward alone: dx [B][NA][NB][C] from x and dy of that shape (launch_mutual_matching_bwd)
+int cwt_debug_mutual_matching_bwd(cwt_ctx* ctx, const float* x, const float* dy, int B, int NA, int NB, int C,
+                                  float* dx, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(x && dy && dx && B >= 1 && NA >= 1 && NB >= 1 && C >= 1 && C <= 64, "bad arguments");
+  CWT_HIP(hipSetDevice(ctx->device));
+  MmBwdWs mw;
+  int rc;
+  if ((rc = mm_bwd_ws(ctx, B, NA, NB, C, &mw))) return rc;
+  return launch_mutual_matching_bwd(x, dy, B, NA, NB, C, dx, mw, (hipStream_t)stream);
+}
+
 int cwt_debug_occupy(cwt_ctx* ctx, int nwg, int us, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");
   CWT_CHECK(nwg >= 1 && nwg <= 256 && us >= 1 && us <= 100000, "occupy: 1 <= nwg <= 256, 1 <= us <= 100000");

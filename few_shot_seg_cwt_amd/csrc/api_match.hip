@@ -17,7 +17,7 @@ static int mm_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, float** rowmax, flo
   return 0;
 }
 
-static int mm_bwd_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, MmBwdWs* w) {
+int cwt::mm_bwd_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, MmBwdWs* w) {
   const long nrb = cdiv(NA, 16), bc = (long)B * C;
   int rc;
   if ((rc = ws(ctx, "mb.rowmax", bc * NA, &w->rowmax)) || (rc = ws(ctx, "mb.rowarg", bc * NA, &w->rowarg)) ||

@@ -144,6 +144,8 @@ int gemm_f32d(cwt_ctx* ctx, const float* A, const float* Bm, int M, int N, int K
 int readout_gemm(cwt_ctx* ctx, const float* P, const float* vt, int B, int NA, int Cv, int ldp, float* out,
                  hipStream_t st);
 int gemm_nt(cwt_ctx* ctx, const float* A, const float* W, int M, int N, int K, float* C, hipStream_t st);
+// MutualMatching backward's scratch from the pool (api_match.hip; cwt_debug_mutual_matching_bwd shares it)
+int mm_bwd_ws(cwt_ctx* ctx, int B, int NA, int NB, int C, MmBwdWs* w);
 
 // A zeroed ConvSArgs / ConvArgs with the conv's geometry, M and K set (down2, conv_out_size: extract_plan.h)
 template <class Args>

@@ -159,6 +159,19 @@ int cwt_debug_cp4d_layer(cwt_ctx* ctx, const float* x, int B, int hA, int wA, in
  * gout = 10), 2 only it, 3 the channel-chunked kernel (cp4d_nc_dgrad_kernel; gin 10, gout 1..32). */
 int cwt_debug_cp4d_dgrad(cwt_ctx* ctx, const float* g, int B, int hA, int wA, int hB, int wB, int gin, int gout,
                          const float* Wa, const float* Wb, float* dx, int accum, int variant, void* stream);
+/* The layer's weight and bias gradients as cwt_match_corr_backward launches them: x [B][hA*wA][hB*wB][cin]
+ * the layer's input, gm [B][hA*wA][hB*wB][cout] its ReLU-masked output gradient; dWa / dWb [cout][cin][3][3]
+ * and db1 / db2 [cout] (conv1's and conv2's bias gradients, the same sum) are added into.  The form is the one
+ * cwt_debug_cp4d_plan(dir 2) names under the environment at the call (CWT_WGRAD_SCALAR is read per launch);
+ * the partial sums live in the context's workspace of cwt_debug_cp4d_wgrad_part_floats() floats. */
+int cwt_debug_cp4d_wgrad(cwt_ctx* ctx, const float* x, const float* gm, int B, int hA, int wA, int hB, int wB, int cin,
+                         int cout, float* dWa, float* dWb, float* db1, float* db2, void* stream);
+
+/* MutualMatching's backward alone (src/model/match.py:34-53 under autograd): x, dy device [B][NA][NB][C]
+ * (channels last, as cwt_mutual_matching) -> dx of that shape.  A row's / column's maximum sends its
+ * gradient to the first maximal index, as torch.max(dim) does.  C <= 64. */
+int cwt_debug_mutual_matching_bwd(cwt_ctx* ctx, const float* x, const float* dy, int B, int NA, int NB, int C,
+                                  float* dx, void* stream);
 
 /* The consensus layer's launch plan (csrc/cp4d_plan.h), on the host alone (no context, no device
  * call; the CWT_CP4D_*, CWT_DGRAD_SCALAR and CWT_WGRAD_SCALAR knobs are read from the environment as

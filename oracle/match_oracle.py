@@ -20,7 +20,9 @@ import torch.nn.functional as F
 def mutual_matching(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """match.py:21-53: x [B, C, ha, wa, hb, wb]; per channel, the ratio of each score to the
     maximum over the query positions (for its support position) and to the maximum over the
-    support positions (for its query position): x * ((x / maxA) * (x / maxB))."""
+    support positions (for its query position): x * ((x / maxA) * (x / maxB)).
+    Forward only at ties: amax's autograd splits a tied maximum's gradient evenly, the reference's
+    torch.max(dim) sends it to the first maximal index (tests/match_ref.py: mutual_matching_first)."""
     B, C, ha, wa, hb, wb = x.shape
     m = x.reshape(B, C, ha * wa, hb * wb)
     max_over_q = m.amax(dim=2, keepdim=True)   # for every support position
