@@ -89,6 +89,10 @@ SIGNATURES = {
     "cwt_weight_average_backward_drop": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                               _P, _P, _P, _F, _F, C.c_uint64, _P]),
     "cwt_seg_head_loss": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    # train_cca.py:177-198: classifier, upsample, compress_pred, SegLoss(., 'pb') and d loss / d f
+    "cwt_seg_head_loss_nway": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    # train_cca.py:347, 353: pred_q2, the softmax mix, as a binary mask against the target
+    "cwt_seg_metrics_nway_mix": (_I, [_P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cwt_mmn_blend_backward": (_I, [_P, _P, _P, _I, _I64, _F, _P, _P, _P]),
     "cwt_linear_backward": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
     "cwt_deform_attn_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

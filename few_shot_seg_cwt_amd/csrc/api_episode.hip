@@ -522,6 +522,61 @@ int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h
   return rc;
 }
 
+int cwt_seg_head_loss_nway(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C, int N,
+                           const int64_t* target, int S, int idx_cls, int loss_type, float* loss_out,
+                           float* logits_out, float* d_f, float* iut_out, void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(W && f && target && loss_out, "null buffer");
+  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+  CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
+  CWT_CHECK(C >= 64 && C % 64 == 0 && C <= 2048, "C must be a multiple of 64, at most 2048");
+  CWT_CHECK(B >= 1 && B <= 8, "need 1 <= B <= 8");
+  CWT_CHECK(h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) / N && S <= 32768, "need h, w, S >= 2");
+  CWT_CHECK(loss_type >= 0 && loss_type <= 2, "loss_type: 0 wt_ce, 1 wt_dc, 2 ce");
+  CWT_HIP(hipSetDevice(ctx->device));
+  const hipStream_t st = (hipStream_t)stream;
+  float *lg, *sc, *pix = nullptr;
+  void* part;
+  int rc;
+  if ((rc = ws(ctx, "shn.logits", (size_t)B * h * w * N, &lg)) ||
+      (rc = ensure_ws(ctx, "shn.part", seg_head_loss_nway_part_bytes(B), &part)) ||
+      (rc = ws(ctx, "shn.sc", seg_head_loss_nway_sc_floats(B), &sc)) ||
+      (d_f && (rc = ws(ctx, "shn.pix", seg_head_loss_nway_pix_floats(B, S), &pix))))
+    return rc;
+  // classifier N x 2*C per pixel (+ the same for d_f); per hi-res pixel N four-tap logits and exponentials, twice
+  Prof p(ctx, st, "seg_head_loss_nway N=" + std::to_string(N),
+         (double)B * h * w * 2.0 * N * C * (d_f ? 2 : 1) + 20.0 * N * B * S * S * (d_f ? 2 : 1),
+         4.0 * B * h * w * C * (d_f ? 2 : 1) + 8.0 * B * S * S * (d_f ? 2 : 1) + (d_f ? 24.0 * B * S * S : 0.0));
+  // the low-resolution logits are cwt_linear's own, pixel-major [B*h*w][N]
+  if ((rc = cwt_linear(ctx, f, (int64_t)B * h * w, C, W, nullptr, N, 0, 0, lg, stream))) return rc;
+  rc = launch_seg_head_loss_nway(W, lg, B, N, h, w, C, target, S, idx_cls, loss_type, loss_out, logits_out, d_f,
+                                 iut_out, part, sc, pix, st);
+  p.end();
+  return rc;
+}
+
+int cwt_seg_metrics_nway_mix(cwt_ctx* ctx, const float* logits0, const float* logits1, double att_wt,
+                             const int64_t* target, int B, int N, int h, int w, int S, int idx_cls, float* iut_out,
+                             void* stream) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(logits0 && logits1 && target && iut_out, "null buffer");
+  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+  CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
+  CWT_CHECK(B >= 1 && B <= 64 && h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) && S <= 32768,
+            "need 1 <= B <= 64 and h, w, S >= 2");
+  CWT_CHECK(att_wt >= 0.0 && att_wt <= 1.0, "att_wt must be in [0, 1]");
+  CWT_HIP(hipSetDevice(ctx->device));
+  void* cnt;
+  int rc;
+  if ((rc = ensure_ws(ctx, "nway.metrics", nway_metrics_ws_bytes(B), &cnt))) return rc;
+  Prof p(ctx, (hipStream_t)stream, "seg_metrics_nway_mix N=" + std::to_string(N), 120.0 * B * N * S * S,
+         8.0 * B * S * S + 8.0 * B * N * h * w);
+  rc = launch_seg_metrics_nway_mix(logits0, logits1, att_wt, target, B, N, h, w, S, idx_cls, iut_out, cnt,
+                                   (hipStream_t)stream);
+  p.end();
+  return rc;
+}
+
 int cwt_iou_preds(cwt_ctx* ctx, const int64_t* preds, const int64_t* target, int64_t n, int num_classes,
                   int ignore_index, float* iut_out, void* stream) {
   if (!ctx) return fail(CWT_EARG, "ctx is NULL");

@@ -333,6 +333,10 @@ int launch_relabel_support(const float* logits, const int64_t* s_label, int B, i
 size_t nway_metrics_ws_bytes(int B);
 int launch_seg_metrics_nway(const float* logits, const int64_t* target, int B, int N, int h, int w, int S,
                             int idx_cls, float* iut, double* ce, void* ws, hipStream_t st);
+// pred_q2 (train_cca.py:347, 353): the mask argmax(softmax(z0) (1 - att_wt) + softmax(z1) att_wt) == idx_cls
+// against the target.  ws: nway_metrics_ws_bytes(B) bytes
+int launch_seg_metrics_nway_mix(const float* logits0, const float* logits1, double att_wt, const int64_t* target, int B,
+                                int N, int h, int w, int S, int idx_cls, float* iut, void* ws, hipStream_t st);
 
 // ---- seg.hip ----
 int launch_normalize(const float* f, int B, int Pb, float* out, const float* W0, float* logits0, hipStream_t st);
@@ -360,6 +364,18 @@ size_t seg_head_loss_part_doubles(int B);
 size_t seg_head_loss_sc_floats(int B);
 int launch_seg_head_loss(const float* W, const float* logits, int B, int h, int w, int C, const int64_t* target, int S,
                          int loss_type, float* loss_out, float* d_f, double* part, float* sc, hipStream_t st);
+
+// ---- seg_loss_nway.hip ----
+// The compressed N-way loss head (train_cca.py:177-198) on pixel-major logits [B][h*w][N].
+// part_ws: seg_head_loss_nway_part_bytes(B) bytes; sc: seg_head_loss_nway_sc_floats(B) floats;
+// pix: seg_head_loss_nway_pix_floats(B, S) floats (read and written only when d_f is given)
+size_t seg_head_loss_nway_part_bytes(int B);
+size_t seg_head_loss_nway_sc_floats(int B);
+size_t seg_head_loss_nway_pix_floats(int B, int S);
+int launch_seg_head_loss_nway(const float* W, const float* logits, int B, int N, int h, int w, int C,
+                              const int64_t* target, int S, int idx_cls, int loss_type, float* loss_out,
+                              float* logits_out, float* d_f, float* iut_out, void* part_ws, float* sc, float* pix,
+                              hipStream_t st);
 
 // ---- cwt_attn.hip ----
 size_t attention_fold_floats(int C, int H);

@@ -198,4 +198,81 @@ int launch_seg_metrics_nway(const float* logits, const int64_t* target, int B, i
   return 0;
 }
 
+// pred_q2 (train_cca.py:347, 353): m = softmax(z0) (1 - att_wt) + softmax(z1) att_wt on the two
+// upsampled logit tensors, the mask argmax_c m == idx_cls (the first maximal index).  Three sweeps
+// over the classes per pixel (the maxima, the exponential sums, the mix), nothing kept per class.
+// Writes seg_metrics_nway_kernel's per-block counts (and zero NLL partials) for the same final kernel.
+__global__ __launch_bounds__(256) void seg_metrics_nway_mix_kernel(const float* __restrict__ logits0,
+                                                                   const float* __restrict__ logits1, double att_wt,
+                                                                   const int64_t* __restrict__ target, int N, int h,
+                                                                   int w, int S, int idx_cls,
+                                                                   unsigned* __restrict__ counts,
+                                                                   double* __restrict__ cep) {
+  __shared__ unsigned cnt[4][6];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int b = blockIdx.y;
+  const long npix = (long)S * S, plane = (long)h * w;
+  const float* L0 = logits0 + (long)b * N * plane;
+  const float* L1 = logits1 + (long)b * N * plane;
+  const double w0 = 1.0 - att_wt, w1 = att_wt;
+  unsigned c6[6] = {0, 0, 0, 0, 0, 0};
+  for (long i = (long)blockIdx.x * 256 + t; i < npix; i += (long)gridDim.x * 256) {
+    const int64_t tg = target[(long)b * npix + i];
+    if (tg == 255) continue;
+    const int Y = (int)(i / S), X = (int)(i - (long)Y * S);
+    const PixelTaps tp = pixel_taps(Y, X, h, w, S);
+    double m0 = tp.at(L0), m1 = tp.at(L1);
+    for (int c = 1; c < N; ++c) {
+      m0 = fmax(m0, tp.at(L0 + c * plane));
+      m1 = fmax(m1, tp.at(L1 + c * plane));
+    }
+    double s0 = 0.0, s1 = 0.0;
+    for (int c = 0; c < N; ++c) {
+      s0 += exp(tp.at(L0 + c * plane) - m0);
+      s1 += exp(tp.at(L1 + c * plane) - m1);
+    }
+    int am = 0;
+    double best = 0.0;
+    for (int c = 0; c < N; ++c) {
+      const double v = exp(tp.at(L0 + c * plane) - m0) / s0 * w0 + exp(tp.at(L1 + c * plane) - m1) / s1 * w1;
+      if (c == 0 || v > best) {  // the first maximal index
+        best = v;
+        am = c;
+      }
+    }
+    const int pred = am == idx_cls ? 1 : 0;
+    c6[2 + pred]++;
+    if (tg == 0 || tg == 1) {
+      c6[4 + (int)tg]++;
+      if (pred == tg) c6[pred]++;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    for (int o = 32; o > 0; o >>= 1) c6[k] += __shfl_xor(c6[k], o, 64);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cnt[wv][k] = c6[k];
+  }
+  __syncthreads();
+  const long pb = (long)b * gridDim.x + blockIdx.x;
+  if (t < 6) counts[pb * 6 + t] = cnt[0][t] + cnt[1][t] + cnt[2][t] + cnt[3][t];
+  if (t < 2) cep[pb * 2 + t] = 0.0;
+}
+
+int launch_seg_metrics_nway_mix(const float* logits0, const float* logits1, double att_wt, const int64_t* target, int B,
+                                int N, int h, int w, int S, int idx_cls, float* iut, void* ws, hipStream_t st) {
+  const long npix = (long)S * S;
+  const int nblk = (int)std::min<long>(NPX_MAXBLK, cdiv(npix, 256));
+  double* cep = (double*)ws;  // the layout of launch_seg_metrics_nway
+  unsigned* counts = (unsigned*)(cep + (long)B * NPX_MAXBLK * 2);
+  hipLaunchKernelGGL(seg_metrics_nway_mix_kernel, dim3(nblk, B), dim3(256), 0, st, logits0, logits1, att_wt, target, N,
+                     h, w, S, idx_cls, counts, cep);
+  CWT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(seg_metrics_nway_final_kernel, dim3(B), dim3(NPX_MAXBLK), 0, st, (const unsigned*)counts,
+                     (const double*)cep, nblk, iut, (double*)nullptr);
+  CWT_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace cwt

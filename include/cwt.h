@@ -415,6 +415,50 @@ int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h
                       const int64_t* target, int S, int loss_type, float* loss_out, float* logits_out,
                       float* d_f, void* stream);
 
+/*
+ * The class-incremental trainer's loss head in one call (src/train_cca.py:177-198): logits = W . f
+ * over N classes (as cwt_linear gives them, bit for bit), the bilinear align_corners=True upsample
+ * to the S x S label, p = softmax_N(z)[idx_cls], q = [1 - p, p] (compress_pred(., idx_cls, 'lg'),
+ * src/model/model_util.py:158-166; F.softmax without dim on a 4-D tensor is dim = 1),
+ * SegLoss(loss_type)(q, target, 'pb') (model_util.py:9-73) and the gradient of the loss w.r.t. f.
+ * W is a constant (the trainer never optimises it).  The reference's arithmetic is kept as it is:
+ * loss_type 1 'wt_dc' (= 'dc'): weighted_dice_loss on q without the sigmoid, t_k = [label == k],
+ *   loss = sum_{b,k} (1 - 2 sum(t q) / max(sum(q^2) + sum(t), 1e-8)) / B (pixels labelled 255 have
+ *   t = 0 in both channels and still count in sum(q^2));
+ * loss_type 2 'ce' and 0 'wt_ce': SegLoss.forward ignores input_type on these branches, so the
+ *   two-channel probabilities q enter CrossEntropyLoss(ignore_index 255) as if they were logits
+ *   (nll = log(exp(q_0) + exp(q_1)) - q_y); 'wt_ce' weights class 1 by #bg / #fg of the target.
+ * N = 2, idx_cls = 1 is a legal call and is not cwt_seg_head_loss: p is a softmax over the two
+ * classes, not a sigmoid per channel.
+ * W device [N][C]; f device NHWC [B][h][w][C]; target device int64 [B][S][S] in {0, 1, 255};
+ * loss_out device fp32 [1]; logits_out device [B][N][h][w] or NULL; d_f device [B][h][w][C] or NULL
+ * (overwritten); iut_out device fp32 [B][3][2] or NULL: intersection, union and target counts of
+ * the mask p > 1 - p against the target (train_cca.py:211-213: pred.argmax(1) of the compressed
+ * prediction, a tie at 0.5 goes to class 0, 255 ignored as in intersectionAndUnionGPU) -- not
+ * pred2bmask's argmax == idx_cls.
+ * 2 <= N <= 64, 0 <= idx_cls < N; C a multiple of 64, at most 2048; 1 <= B <= 8; h, w, S >= 2 (any
+ * ratio), h*w*N <= 2^24; CWT_EARG otherwise.  The S x S x N logits are never stored.  Every float
+ * sum runs in a fixed order (no float atomics), the counts are integers: two calls on the same
+ * inputs give the same bits.  No host sync.
+ */
+int cwt_seg_head_loss_nway(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C, int N,
+                           const int64_t* target, int S, int idx_cls, int loss_type, float* loss_out,
+                           float* logits_out, float* d_f, float* iut_out, void* stream);
+
+/*
+ * pred_q2 of the class-incremental validation (src/train_cca.py:347, 353): both N-way logit
+ * tensors [B,N,h,w] are upsampled to S x S (bilinear, align_corners=True),
+ *   m = softmax_N(z0) (1 - att_wt) + softmax_N(z1) att_wt,
+ * and the mask argmax_c m == idx_cls (first maximal index; pred2bmask) is counted against the
+ * 0 / 1 / 255 target as in cwt_seg_metrics_nway: iut_out device fp32 [B,3,2].  Interpolation and
+ * softmaxes in float64 on the fp32 logits, integer counts summed in block order: bitwise
+ * reproducible.  att_wt = 0 gives cwt_seg_metrics_nway's counts on logits0.
+ * Limits as cwt_seg_metrics_nway's, and 0 <= att_wt <= 1; CWT_EARG otherwise.
+ */
+int cwt_seg_metrics_nway_mix(cwt_ctx* ctx, const float* logits0, const float* logits1, double att_wt,
+                             const int64_t* target, int B, int N, int h, int w, int S, int idx_cls, float* iut_out,
+                             void* stream);
+
 /* intersectionAndUnionGPU on argmax maps (util.py:280-308): preds/target device int64 [n];
  * preds[target==ignore] take the ignore index, as in the reference: with ignore_index outside
  * [0, num_classes) those pixels count nowhere, with one inside they count as intersection,
