@@ -494,15 +494,27 @@ int cwt_seg_ce_fwd_bwd(cwt_ctx* ctx, const float* logits, const int64_t* target,
                        (double*)num, (hipStream_t)stream);
 }
 
+// the two loss heads' argument checks; nway: the head that takes N and idx_cls (its logits hold N floats a pixel)
+static int check_head_args(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C,
+                           const int64_t* target, int S, int loss_type, const float* loss_out, bool nway, int N,
+                           int idx_cls) {
+  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
+  CWT_CHECK(W && f && target && loss_out, "null buffer");
+  if (nway) {
+    CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
+    CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
+  }
+  CWT_CHECK(C >= 64 && C % 64 == 0 && C <= 2048, "C must be a multiple of 64, at most 2048");
+  CWT_CHECK(B >= 1 && B <= 8, "need 1 <= B <= 8");
+  CWT_CHECK(h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) / (nway ? N : 1) && S <= 32768, "need h, w, S >= 2");
+  CWT_CHECK(loss_type >= 0 && loss_type <= 2, "loss_type: 0 wt_ce, 1 wt_dc, 2 ce");
+  return 0;
+}
+
 int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C,
                       const int64_t* target, int S, int loss_type, float* loss_out, float* logits_out, float* d_f,
                       void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(W && f && target && loss_out, "null buffer");
-  CWT_CHECK(C >= 64 && C % 64 == 0 && C <= 2048, "C must be a multiple of 64, at most 2048");
-  CWT_CHECK(B >= 1 && B <= 8, "need 1 <= B <= 8");
-  CWT_CHECK(h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) && S <= 32768, "need h, w, S >= 2");
-  CWT_CHECK(loss_type >= 0 && loss_type <= 2, "loss_type: 0 wt_ce, 1 wt_dc, 2 ce");
+  if (int bad = check_head_args(ctx, W, f, B, h, w, C, target, S, loss_type, loss_out, false, 2, 1)) return bad;
   CWT_HIP(hipSetDevice(ctx->device));
   const hipStream_t st = (hipStream_t)stream;
   float *lg, *sc;
@@ -525,14 +537,7 @@ int cwt_seg_head_loss(cwt_ctx* ctx, const float* W, const float* f, int B, int h
 int cwt_seg_head_loss_nway(cwt_ctx* ctx, const float* W, const float* f, int B, int h, int w, int C, int N,
                            const int64_t* target, int S, int idx_cls, int loss_type, float* loss_out,
                            float* logits_out, float* d_f, float* iut_out, void* stream) {
-  if (!ctx) return fail(CWT_EARG, "ctx is NULL");
-  CWT_CHECK(W && f && target && loss_out, "null buffer");
-  CWT_CHECK(N >= 2 && N <= CWT_ADAPT_MAX_WAY, "N must be in [2, 64]");
-  CWT_CHECK(idx_cls >= 0 && idx_cls < N, "idx_cls must be in [0, N)");
-  CWT_CHECK(C >= 64 && C % 64 == 0 && C <= 2048, "C must be a multiple of 64, at most 2048");
-  CWT_CHECK(B >= 1 && B <= 8, "need 1 <= B <= 8");
-  CWT_CHECK(h >= 2 && w >= 2 && S >= 2 && (long)h * w <= (1L << 24) / N && S <= 32768, "need h, w, S >= 2");
-  CWT_CHECK(loss_type >= 0 && loss_type <= 2, "loss_type: 0 wt_ce, 1 wt_dc, 2 ce");
+  if (int bad = check_head_args(ctx, W, f, B, h, w, C, target, S, loss_type, loss_out, true, N, idx_cls)) return bad;
   CWT_HIP(hipSetDevice(ctx->device));
   const hipStream_t st = (hipStream_t)stream;
   float *lg, *sc, *pix = nullptr;
@@ -540,7 +545,7 @@ int cwt_seg_head_loss_nway(cwt_ctx* ctx, const float* W, const float* f, int B, 
   int rc;
   if ((rc = ws(ctx, "shn.logits", (size_t)B * h * w * N, &lg)) ||
       (rc = ensure_ws(ctx, "shn.part", seg_head_loss_nway_part_bytes(B), &part)) ||
-      (rc = ws(ctx, "shn.sc", seg_head_loss_nway_sc_floats(B), &sc)) ||
+      (rc = ws(ctx, "shn.sc", seg_head_loss_sc_floats(B), &sc)) ||
       (d_f && (rc = ws(ctx, "shn.pix", seg_head_loss_nway_pix_floats(B, S), &pix))))
     return rc;
   // classifier N x 2*C per pixel (+ the same for d_f); per hi-res pixel N four-tap logits and exponentials, twice

@@ -359,7 +359,8 @@ int launch_sgd(float* p, const float* g, float* buf, long n, float lr, float mom
                hipStream_t st);
 
 // ---- seg_loss.hip ----
-// part: [B][SHL_MAXBLK][6] doubles (per-block partial sums); sc: [B][4] + [4] floats
+// The two loss heads and nway_pixel.hip stand on pixel_pass.h (PIX_MAXBLK blocks per image).
+// part: [B][PIX_MAXBLK][6] doubles (per-block partial sums); sc (both heads): [B][4] + [4] floats
 size_t seg_head_loss_part_doubles(int B);
 size_t seg_head_loss_sc_floats(int B);
 int launch_seg_head_loss(const float* W, const float* logits, int B, int h, int w, int C, const int64_t* target, int S,
@@ -367,10 +368,9 @@ int launch_seg_head_loss(const float* W, const float* logits, int B, int h, int 
 
 // ---- seg_loss_nway.hip ----
 // The compressed N-way loss head (train_cca.py:177-198) on pixel-major logits [B][h*w][N].
-// part_ws: seg_head_loss_nway_part_bytes(B) bytes; sc: seg_head_loss_nway_sc_floats(B) floats;
+// part_ws: seg_head_loss_nway_part_bytes(B) bytes; sc: seg_head_loss_sc_floats(B) floats;
 // pix: seg_head_loss_nway_pix_floats(B, S) floats (read and written only when d_f is given)
 size_t seg_head_loss_nway_part_bytes(int B);
-size_t seg_head_loss_nway_sc_floats(int B);
 size_t seg_head_loss_nway_pix_floats(int B, int S);
 int launch_seg_head_loss_nway(const float* W, const float* logits, int B, int N, int h, int w, int C,
                               const int64_t* target, int S, int idx_cls, int loss_type, float* loss_out,

@@ -71,6 +71,7 @@ for _ in range(steps):
 med = lambda v: round(sorted(v)[len(v) // 2], 3)  # noqa: E731
 out = {"h": h, "S": S, "shots": shots, "steps": steps, "att_drop": 0.5, "proj_drop": 0.5, "aux": aux}
 out.update({p + "_ms": med(v) for p, v in ts.items()})
+out.update({"loss_head_min_ms": round(min(ts["loss_head"]), 3), "loss_head_max_ms": round(max(ts["loss_head"]), 3)})
 out["loss_head_share"] = round(out["loss_head_ms"] / out["step_ms"], 4)
 line = json.dumps(out)
 print(line)
