@@ -93,6 +93,19 @@ SIGNATURES = {
     "cwt_seg_head_loss_nway": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     # train_cca.py:347, 353: pred_q2, the softmax mix, as a binary mask against the target
     "cwt_seg_metrics_nway_mix": (_I, [_P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # train_fuse.py:121-229: FuseNet1's 4-D stack, support mask, mask-in-bias, softmax, blend, loss head
+    "cwt_fuse_stack_saved_floats": (_I64, [_I, _I, _I, _I, _I]),
+    "cwt_fuse_stack": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
+    "cwt_fuse_stack_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I64, _I, _I, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P]),
+    "cwt_fuse_support_mask": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "cwt_fuse_mask_bias": (_I, [_P, _P, _I64, _I, _P, _I, _P, _I, _P, _P]),
+    "cwt_fuse_mask_bias_backward": (_I, [_P, _P, _P, _I, _I, _P, _I64, _I, _P]),
+    "cwt_fuse_softmax2": (_I, [_P, _P, _I, _I64, _P, _P]),
+    "cwt_fuse_softmax2_backward": (_I, [_P, _P, _P, _I, _I64, _P, _P]),
+    "cwt_fuse_blend": (_I, [_P, _P, _P, _P, _I, _I64, _I, _P, _P]),
+    "cwt_fuse_blend_backward": (_I, [_P, _P, _P, _P, _I, _I64, _I, _P, _P]),
+    "cwt_fuse_loss_head": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "cwt_mmn_blend_backward": (_I, [_P, _P, _P, _I, _I64, _F, _P, _P, _P]),
     "cwt_linear_backward": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
     "cwt_deform_attn_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

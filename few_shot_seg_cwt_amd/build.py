@@ -20,8 +20,8 @@ SOURCES = ["api.hip", "api_extract.hip", "api_episode.hip", "api_heads.hip", "ap
            "conv.hip", "conv_x3s.hip", "backbone.hip", "adapt.hip", "cwt_attn.hip", "seg.hip",
            "bn_train.hip", "preprocess.hip", "heads.hip", "match.hip", "cp4d.hip", "detr.hip", "pretrain_kernels.hip",
            "pretrain.hip", "tail.hip", "match_bwd.hip", "wino.hip", "conv_x6.hip", "seg_loss.hip",
-           "adapt_nway.hip", "nway_pixel.hip", "seg_loss_nway.hip"]
-HEADERS = ["common.h", "kernels.h", "adapt_plan.h", "cp4d_plan.h", "match_plan.h", "backbone_arch.h", "extract_plan.h", "ctx.h", "pretrain.h", "conv_plans_x3s.inc", "conv_plans_b16.inc", "conv_plans_f32.inc", "conv_plans_f32d.inc", "conv_plans_x6.inc", "conv_body.h", "conv_forms.h", "tail_body.h", "pixel_pass.h"]
+           "adapt_nway.hip", "nway_pixel.hip", "seg_loss_nway.hip", "fuse.hip", "api_fuse.hip"]
+HEADERS = ["common.h", "kernels.h", "adapt_plan.h", "cp4d_plan.h", "match_plan.h", "backbone_arch.h", "extract_plan.h", "ctx.h", "pretrain.h", "conv_plans_x3s.inc", "conv_plans_b16.inc", "conv_plans_f32.inc", "conv_plans_f32d.inc", "conv_plans_x6.inc", "conv_body.h", "conv_forms.h", "tail_body.h", "pixel_pass.h", "fuse.h"]
 PUBLIC_HEADERS = ["cwt.h", "cwt_debug.h"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -256,3 +256,7 @@ class MultiHeadAttentionOne(torch.nn.Module):
             grad_flat = self.flat.grad
         self._bwd(q, f, saved, d_out.contiguous(), grad_flat, drop=drop)
         return grad_flat
+
+
+# the fusion trainer's weighting net (transformer.py:286-330 of the reference) lives in fuse.py
+from .fuse import FuseNet1  # noqa: E402,F401

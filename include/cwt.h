@@ -816,6 +816,81 @@ int cwt_pretrain_get(cwt_pretrain* pt, const char* name, int what, float* host_o
 int cwt_pretrain_set(cwt_pretrain* pt, const char* name, int what, const float* host_in, int64_t numel);
 int cwt_pretrain_num_params(const cwt_pretrain* pt, int64_t* total, int64_t* backbone);
 
+/* ---- The fusion trainer (src/train_fuse.py, scripts/train_fuse.sh): FuseNet1 over a frozen MatchNet ----
+ *
+ * Replaces: FuseNet1.conv4d on one correlation and the reshape / permute / cat that follow it
+ * (src/model/transformer.py:292-297, :313-316, :326; CenterPivotConv4d, src/model/conv4d.py:27-62).
+ * corr device [B][hA*wA][hB*wB] fp32 -> CenterPivotConv4d(1, 16, stride (1,1,2,2)), ReLU,
+ * CenterPivotConv4d(16, 1), ReLU -> y2 [B][hA*wA][mB*nB], mB = ceil(hB/2), nB = ceil(wB/2), written to
+ * X[(b hA wA + a) ldx + col + b'] (X device [B][hA*wA][ldx]: the attention net's token matrix; every
+ * other column is left alone).  w1a / b1a = conv4d.0.conv1 (weight [16][1][3][3] over the query plane,
+ * bias [16]), w1b / b1b = conv4d.0.conv2 (the strided support plane), w2a / b2a / w2b / b2b =
+ * conv4d.2.conv1 / conv2 (weight [1][16][3][3], bias [1]); all device fp32 in PyTorch's layout.
+ * y1_saved NULL: layer 1 is recomputed on each output's cross-shaped halo and never stored (eval).
+ * y1_saved device [cwt_fuse_stack_saved_floats]: layer 1's output after its ReLU, [B][hA*wA][mB*nB][16],
+ * for cwt_fuse_stack_backward; its signs are layer 1's ReLU gates, X's are layer 2's.  Both forms
+ * give the same bits.  Sides >= 2.  Exact fp32 (FMA), fixed summation order.  Arguments are checked
+ * before the context (every cwt_fuse_* entry): a refusal needs no device. */
+int64_t cwt_fuse_stack_saved_floats(int B, int hA, int wA, int hB, int wB);
+int cwt_fuse_stack(cwt_ctx* ctx, const float* corr, int B, int hA, int wA, int hB, int wB, const float* w1a,
+                   const float* b1a, const float* w1b, const float* b1b, const float* w2a, const float* b2a,
+                   const float* w2b, const float* b2b, float* y1_saved, float* X, int64_t ldx, int col, void* stream);
+
+/* Replaces: autograd through FuseNet1.conv4d (train_fuse.py:189; the correlations carry no gradient:
+ * l_corr comes from the frozen MatchNet under no_grad, :167-169, h_corr has no parameter upstream).
+ * d_X device: the gradient at X (same ldx / col as the forward); X holds the forward's y2.  Writes the
+ * eight parameter gradients (layouts of the parameters; conv1's and conv2's bias of a layer receive the
+ * same sum); accumulate != 0 adds to what they hold (the second correlation of train_fuse.py:177
+ * shares the weights).  Fixed-order sums, no atomics: two calls give the same bits. */
+int cwt_fuse_stack_backward(cwt_ctx* ctx, const float* corr, int B, int hA, int wA, int hB, int wB, const float* w2a,
+                            const float* w2b, const float* y1_saved, const float* X, const float* d_X, int64_t ldx,
+                            int col, int accumulate, float* d_w1a, float* d_b1a, float* d_w1b, float* d_b1b,
+                            float* d_w2a, float* d_b2a, float* d_w2b, float* d_b2b, void* stream);
+
+/* Replaces: s_mask = clone(s_label); s_mask[s_mask == 255] = 0; F.interpolate(s_mask.float(), (m, m),
+ * 'bilinear', align_corners) (train_fuse.py:173-175 with align_corners=True; :319-321 with the default,
+ * False).  label device [H][W] int64 -> s_mask device [m][m] fp32.  pool != 0: the resize goes to
+ * [2m][2m] and FuseNet1's AvgPool2d(2, 2) follows (transformer.py:298, :318-319). */
+int cwt_fuse_support_mask(cwt_ctx* ctx, const int64_t* label, int H, int W, int m, int align_corners, int pool,
+                          float* s_mask, void* stream);
+
+/* Replaces: the broadcast support mask's m^2 input channels of FuseNet1.att[0] (transformer.py:320-321,
+ * :326-327), never materialised: b_eff[j] = b[j] + sum_i W[j ldw + col + i] s_mask[i], j < mid, i < n.
+ * The backward: d_W[j ldw + col + i] = d_b[j] s_mask[i], d_b the bias gradient (the sum over the pixels
+ * of the hidden layer's gradient). */
+int cwt_fuse_mask_bias(cwt_ctx* ctx, const float* W, int64_t ldw, int col, const float* s_mask, int n, const float* b,
+                       int mid, float* b_eff, void* stream);
+int cwt_fuse_mask_bias_backward(cwt_ctx* ctx, const float* d_b, const float* s_mask, int mid, int n, float* d_W,
+                                int64_t ldw, int col, void* stream);
+
+/* Replaces: F.softmax(wt, dim=1) of the two attention logits (transformer.py:328) and its backward.
+ * z / d_z device [B][P][2] (tokens), wt / d_wt device [B][2][P] (planes, the reference's [B, 2, h, w]). */
+int cwt_fuse_softmax2(cwt_ctx* ctx, const float* z, int B, int64_t P, float* wt, void* stream);
+int cwt_fuse_softmax2_backward(cwt_ctx* ctx, const float* wt, const float* d_wt, int B, int64_t P, float* d_z,
+                               void* stream);
+
+/* Replaces: out = weighted_v * wt[:, 0:1] + f_q * wt[:, 1:2] (train_fuse.py:178, :324) on NHWC tokens
+ * wv / f_q / out device [B][P][C], wt device [B][2][P]; the backward gives d_wt [B][2][P] =
+ * {sum_c d_out wv, sum_c d_out f_q} (wv and f_q carry no gradient: both come out of no_grad). */
+int cwt_fuse_blend(cwt_ctx* ctx, const float* wv, const float* f_q, const float* wt, int B, int64_t P, int C,
+                   float* out, void* stream);
+int cwt_fuse_blend_backward(cwt_ctx* ctx, const float* wv, const float* f_q, const float* d_out, int B, int64_t P,
+                            int C, float* d_wt, void* stream);
+
+/* Replaces: the three upsamples, wt_mask, the weighted CrossEntropyLoss(ignore_index=255,
+ * reduction='none') and its backward to pd_q, and the three intersectionAndUnionGPU calls
+ * (train_fuse.py:155, :171, :180-186, :195-205).  pd_q / pd_q0 / pd_q1 device [2][h][w] (blend, plain
+ * classifier, weighted v), label device [S][S] int64.  Per pixel m_i = 1 where argmax(pred_q0) !=
+ * argmax(pred_q1) and label != 255, else 0.001 (ignored pixels count 0.001 in the denominator, as
+ * sum(wt_mask) counts them); loss_out device float = sum ce_i m_i / sum m_i; d_pd_q device [2][h][w]
+ * (or NULL); iut_out device [3][3][2] = {intersection, union, target} x class of pred_q, pred_q0,
+ * pred_q1; disagree_out device float = pixels with m_i = 1.  Float64 per pixel, fixed-order sums.
+ * One call, three launches (per-block sums, the final sums and loss, the gather adjoint), as the other
+ * loss heads here. */
+int cwt_fuse_loss_head(cwt_ctx* ctx, const float* pd_q, const float* pd_q0, const float* pd_q1, int h, int w,
+                       const int64_t* label, int S, float* loss_out, float* d_pd_q, float* iut_out,
+                       float* disagree_out, void* stream);
+
 /*
  * Per-launch profiling (no reference counterpart; measurement support for bench.py).
  * level 1: the context records a hipEvent pair on the call's stream around each whole
